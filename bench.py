@@ -107,6 +107,42 @@ def _cpu_full_record():
     return None
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_ADAPTER_SAMPLE = 1 << 20      # elements of the flat adapter kept by --dump-outputs (the 7B adapter has ~640 M)
+
+
+def dump_outputs(out_dir, micro, opt, work, rank):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy in float32 / float64 - per-token log-probs of the
+    policy and of the frozen reference, DPO loss and rewards (micro-batches of the step concatenated), the post-clip gradient norm, and
+    the updated adapter (fp32 master and the bf16 working copy the next step reads) at a fixed, seeded sample of positions.  Inputs are
+    seeded (synth.py), so two builds run with the same arguments can be compared file by file.  Collective under zero1 (the master is
+    assembled from the shards); rank 0 writes."""
+    import numpy as np
+    master = opt._full(opt.p_shard) if opt.sharded else opt.master
+    if rank != 0:
+        return
+    n = work.numel()
+    idx = None
+    if n > DUMP_ADAPTER_SAMPLE:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(0, n, (DUMP_ADAPTER_SAMPLE,), generator=g).sort().values.to(work.device)
+    sample = (lambda t: t if idx is None else t.index_select(0, idx))
+    arrays = {k: torch.cat([m[k] for m in micro]).float()
+              for k in ("policy_chosen_logprobs", "policy_rejected_logprobs", "reference_chosen_logprobs", "reference_rejected_logprobs",
+                        "loss", "chosen_rewards", "rejected_rewards")}
+    arrays["adapter_master_sample"] = sample(master).float()
+    arrays["adapter_work_sample"] = sample(work).float()
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    arrays["grad_norm"] = np.array([opt.grad_norm_post_clip()], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit (fewer --pairs or --accum)")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    print(f"[bench] wrote {len(arrays)} arrays ({total / 1e6:.1f} MB) of the last timed step to {out_dir}", file=sys.stderr, flush=True)
+
+
 def cpu_baseline_config_p(dims_kw, n_layers=1):
     """SURVEY.md §8(d) config (1) timed DIRECTLY on the host cores: 8 pairs, query 32 + response 96 (L = 703), fp32, world 1, the whole
     path of a pair - CLIP tower + projector once per image, frozen-reference forward (no grad) and policy forward on chosen + rejected,
@@ -596,7 +632,12 @@ def main():
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the `thirteen_b` (BASELINE.json configs[3] at 1 GPU) and `recipe` (the reference's native unit: 3 responses, response_len 896, CoPO) sub-records (each runs in a child process after the 7B state is released)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous / exchange self-check without kernels (gloo on a box with fewer GPUs than ranks)")
     ap.add_argument("--backend", default="auto", choices=["auto", "nccl", "gloo"], help="force the process-group backend (gloo: --dry-run on CPU, or the one-device test of the N > 1 path)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the real step; --dry-run runs no kernels")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # no launcher environment: start the ranks ourselves (the driver calls `python bench.py --gpus N` the same way as for N = 1)
         if not args.dry_run and torch.cuda.device_count() < args.gpus and os.environ.get("OPADPO_BENCH_SHARE_DEVICE") != "1":
@@ -682,6 +723,7 @@ def main():
     pool = [synth_pairs(d, args.pairs, q_len, t_len, seed=1000 * rank + i, device=dev) for i in range(n_pool)]
     main_pool, main_opt = pool, opt
     step_no = [0]
+    last_out = [] if args.dump_outputs else None      # --dump-outputs: what the latest step returned, per micro-batch (references, no copies)
 
     def step(pool=None, opt=None, hook=None):
         pool = pool if pool is not None else main_pool
@@ -690,6 +732,8 @@ def main():
         k0 = (step_no[0] * args.accum) % len(pool)
         step_no[0] += 1
         batches = pool[k0:k0 + args.accum]
+        if last_out is not None:
+            last_out.clear()
         for mi, b in enumerate(batches):
             feats = eng.encode_images(b["images"])
             # row_lead / row_lens: the batch's ragged-row plan as the (synthetic) collator produced it on the host - no pass reads
@@ -701,8 +745,13 @@ def main():
             with torch.no_grad():
                 r = ref_policy(**kw)
             o = policy(**kw)
-            loss, _, _ = pair_loss(largs, o["chosen_response_logprobs"], o["rejected_response_logprobs"],
-                                   r["chosen_response_logprobs"], r["rejected_response_logprobs"])
+            loss, c_rew, r_rew = pair_loss(largs, o["chosen_response_logprobs"], o["rejected_response_logprobs"],
+                                           r["chosen_response_logprobs"], r["rejected_response_logprobs"])
+            if last_out is not None:
+                last_out.append({"policy_chosen_logprobs": o["chosen_response_logprobs"].detach(),
+                                 "policy_rejected_logprobs": o["rejected_response_logprobs"].detach(),
+                                 "reference_chosen_logprobs": r["chosen_response_logprobs"], "reference_rejected_logprobs": r["rejected_response_logprobs"],
+                                 "loss": loss.detach().reshape(1), "chosen_rewards": c_rew.detach(), "rejected_rewards": r_rew.detach()})
             policy.layer_done_hook = hook if mi == len(batches) - 1 else None
             loss.backward()
             policy.layer_done_hook = None
@@ -747,6 +796,8 @@ def main():
     if rank == 0 and hasattr(eng, "profile"):
         ctx_prof = eng.profile_read()
         eng.profile(False)
+    if last_out is not None:      # before any side leg steps the model again
+        dump_outputs(args.dump_outputs, last_out, opt, pol_ad.work, rank)
     tmax = torch.tensor([dt], device=dev)
     dist_rec = None
     if world > 1:

@@ -61,3 +61,40 @@ def test_bench_defaults():
     # nothing at run time may read the reference tree
     for f in ("bench.py", "__graft_entry__.py"):
         assert "/root/reference" not in open(os.path.join(REPO, f)).read()
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: one float32 / float64 .npy per returned array, micro-batches concatenated, the adapter reduced to a
+    fixed seeded sample, at most 64 MB in all."""
+    import types
+
+    import numpy as np
+    import torch
+    import bench
+    n = bench.DUMP_ADAPTER_SAMPLE * 3
+    master = torch.randn(n)
+    opt = types.SimpleNamespace(sharded=False, master=master, grad_norm_post_clip=lambda: 0.5)
+
+    def micro(seed):
+        g = torch.Generator().manual_seed(seed)
+        lp = {f"{w}_{k}_logprobs": torch.randn(4, 16, generator=g) for w in ("policy", "reference") for k in ("chosen", "rejected")}
+        return dict(lp, loss=torch.rand(1, generator=g), chosen_rewards=torch.randn(4, 16, generator=g),
+                    rejected_rewards=torch.randn(4, 16, generator=g))
+
+    mbs = [micro(0), micro(1)]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), mbs, opt, master.bfloat16(), rank=0)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(k + ".npy" for k in list(mbs[0]) + ["adapter_master_sample", "adapter_work_sample", "grad_norm"])
+    total = 0
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.array_equal(np.load(tmp_path / "a" / "policy_chosen_logprobs.npy"),
+                          torch.cat([m["policy_chosen_logprobs"] for m in mbs]).numpy())
+    assert np.load(tmp_path / "a" / "loss.npy").shape == (2,) and np.load(tmp_path / "a" / "grad_norm.npy").tolist() == [0.5]
+    ms = np.load(tmp_path / "a" / "adapter_master_sample.npy")
+    assert ms.shape == (bench.DUMP_ADAPTER_SAMPLE,) and np.isin(ms, master.numpy()).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "adapter_work_sample.npy"), torch.from_numpy(ms).bfloat16().float().numpy())

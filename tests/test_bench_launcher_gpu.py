@@ -41,3 +41,22 @@ def test_bench_two_ranks_self_launched(mode):
 def test_bench_one_rank_line_has_no_dist_record():
     d, r = _run("--gpus", "1", "--model", "tiny", "--pairs", "4", "--steps", "2", "--warmup", "1", "--no-side-legs")
     assert "launching" not in r.stderr and "dist" not in d and d["n_gpus"] == 1 and d["value"] > 0
+
+
+def test_bench_dump_outputs_repeat_with_the_same_arguments(tmp_path):
+    """--dump-outputs: the last timed step's arrays are written, `--steps` sets the timed steps, and two runs with the same arguments
+    see the same seeded inputs, so their outputs agree (up to the order of floating-point atomics in the backward)."""
+    import numpy as np
+    argv = ("--gpus", "1", "--model", "tiny", "--pairs", "4", "--steps", "3", "--warmup", "1", "--no-side-legs")
+    runs = [_run(*argv, "--dump-outputs", str(tmp_path / d))[0] for d in ("a", "b")]
+    for d in runs:
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert "policy_chosen_logprobs.npy" in names and "adapter_master_sample.npy" in names and names == sorted(os.listdir(tmp_path / "b"))
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.isfinite(a).all(), f
+        np.testing.assert_allclose(a, b, rtol=1e-4, atol=1e-5, err_msg=f)
+    lp = np.load(tmp_path / "a" / "policy_chosen_logprobs.npy")
+    assert lp.shape == (4, 16) and (lp < 0).any()
+    assert np.load(tmp_path / "a" / "loss.npy")[-1] == pytest.approx(runs[0]["config"]["loss"], rel=1e-6)
