@@ -21,6 +21,7 @@
 // access patterns (row fragments via ds_read_b128, transposed fragments via ds_read_b64_tr_b16):
 //   HD=128 (256-B rows): chunk ^= (row & 7) << 1      HD=64 (128-B rows): chunk ^= ((row >> 1) & 3) << 1
 #include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 #include "common.h"
 #include "kernels.h"
@@ -1442,4 +1443,78 @@ hipError_t launch_attn_bwd(const AttnArgs& a, hipStream_t st) {
   }
 #undef LAUNCH_BWD
   return hipGetLastError();
+}
+
+// ---- test entry points (not part of the ABI in include/opadpo_hip.h) ----------------------------------------------------------------------
+// opadpo_attn_fwd / _bwd with the fields only opadpo_ctx reaches: ragged rows (seq_meta, meta_stride, n_seg, rows_total; see AttnArgs), the
+// backward's fused inverse rotary embedding (rope_pos, rope_l2theta) and the per-call kernel switch use_tr (-1 = process default; bit 0 =
+// transposed LDS reads, bit 8 = the 16-row forward and dQ kernels, as context flag bit 8).  Every argument is checked before any launch; the
+// metadata is read back to the host for that (the call synchronises its stream).
+namespace {
+int attn_debug_check(const char* fn, const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* o, int ld, int ldo, int S_, int L,
+                     int nh, int hd, int causal, int seg_prefix, int seg_len, const int32_t* seq_meta, int meta_stride, int n_seg, int rows_total,
+                     const int32_t* rope_pos, void* stream) {
+  if (hd != 64 && hd != 128) return opadpo_report_bad(fn, "head_dim must be 64 or 128");
+  if (!q || !k || !v || !o || ld % 8 || ldo % 8) return opadpo_report_bad(fn, "null operand or misaligned leading dimension (ld % 8, ldo % 8)");
+  if (S_ < 0 || L < 0 || nh <= 0 || ld < nh * hd || ldo < nh * hd) return opadpo_report_bad(fn, "bad geometry (S, L >= 0, nh > 0, ld and ldo >= nh * hd)");
+  if (seg_len < 0 || seg_prefix < 0 || (seg_len > 0 && !causal)) return opadpo_report_bad(fn, "packed responses need causal attention and seg_prefix, seg_len >= 0");
+  if (rope_pos && !seq_meta) return opadpo_report_bad(fn, "rope_pos needs ragged metadata");
+  if (!seq_meta) return 0;
+  if (seg_len > 0) return opadpo_report_bad(fn, "ragged metadata and padded packed responses (seg_len > 0) exclude each other");
+  if (n_seg < 0 || meta_stride < n_seg + 2 || rows_total <= 0) return opadpo_report_bad(fn, "ragged metadata needs n_seg >= 0, meta_stride >= n_seg + 2, rows_total > 0");
+  if (n_seg > 0 && !causal) return opadpo_report_bad(fn, "packed responses need causal attention");
+  if (S_ == 0) return 0;
+  int32_t* m = (int32_t*)malloc((size_t)S_ * meta_stride * sizeof(int32_t));
+  if (!m) return opadpo_report_done(hipErrorOutOfMemory, fn);
+  hipError_t e = hipMemcpyAsync(m, seq_meta, (size_t)S_ * meta_stride * sizeof(int32_t), hipMemcpyDefault, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  if (e != hipSuccess) { free(m); return opadpo_report_done(e, fn); }
+  const char* what = nullptr;
+  for (int s = 0; s < S_ && !what; ++s) {
+    const int32_t* r = m + (size_t)s * meta_stride;
+    if (r[0] < 0 || r[1] < 0) { what = "ragged metadata: negative first row or prefix end"; break; }
+    for (int a = 1; a <= n_seg; ++a)
+      if (r[1 + a] < r[a]) { what = "ragged metadata: segment boundaries must be non-decreasing"; break; }
+    if (what) break;
+    if (r[1 + n_seg] > L) what = "ragged metadata: a sequence is longer than L";
+    else if ((int64_t)r[0] + r[1 + n_seg] > rows_total) what = "ragged metadata: rows_total is smaller than the end of a sequence";
+  }
+  free(m);
+  return what ? opadpo_report_bad(fn, what) : 0;
+}
+}  // namespace
+
+extern "C" int opadpo_debug_attn_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, int ld, uint16_t* o, int ldo, float* lse,
+                                     const uint8_t* key_mask, int S_, int L, int nh, int hd, int causal, float scale, int seg_prefix, int seg_len,
+                                     const int32_t* seq_meta, int meta_stride, int n_seg, int rows_total, int use_tr, void* stream) {
+  const char* fn = "opadpo_debug_attn_fwd";
+  if (const int rc = attn_debug_check(fn, q, k, v, o, ld, ldo, S_, L, nh, hd, causal, seg_prefix, seg_len, seq_meta, meta_stride, n_seg,
+                                      rows_total, nullptr, stream)) return rc;
+  AttnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse; a.key_mask = key_mask;
+  a.S = S_; a.L = L; a.nh = nh; a.hd = hd; a.ld = ld; a.ldo = ldo; a.causal = causal; a.scale = scale;
+  a.seg_prefix = seg_prefix; a.seg_len = seg_len; a.use_tr = use_tr;
+  if (seq_meta) { a.seq_meta = seq_meta; a.meta_stride = meta_stride; a.n_seg = n_seg; a.rows_total = rows_total; }
+  return opadpo_report_done(launch_attn_fwd(a, (hipStream_t)stream), fn);
+}
+
+extern "C" int opadpo_debug_attn_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, int ld, const uint16_t* o, const uint16_t* dout,
+                                     int ldo, const float* lse, const uint8_t* key_mask, uint16_t* dq, uint16_t* dk, uint16_t* dv, float* dq_f32,
+                                     float* delta, int S_, int L, int nh, int hd, int causal, float scale, int seg_prefix, int seg_len,
+                                     const int32_t* seq_meta, int meta_stride, int n_seg, int rows_total, const int32_t* rope_pos,
+                                     float rope_l2theta, int use_tr, void* stream) {
+  const char* fn = "opadpo_debug_attn_bwd";
+  if (!dout || !lse || (!dq && !dq_f32) || !dk || !dv || !delta) return opadpo_report_bad(fn, "null operand");
+  if (const int rc = attn_debug_check(fn, q, k, v, o, ld, ldo, S_, L, nh, hd, causal, seg_prefix, seg_len, seq_meta, meta_stride, n_seg,
+                                      rows_total, rope_pos, stream)) return rc;
+  AttnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q = q; a.k = k; a.v = v; a.o = (uint16_t*)o; a.lse = (float*)lse; a.key_mask = key_mask;
+  a.S = S_; a.L = L; a.nh = nh; a.hd = hd; a.ld = ld; a.ldo = ldo; a.causal = causal; a.scale = scale;
+  a.dout = dout; a.dq_acc = dq_f32; a.dq = dq; a.dk = dk; a.dv = dv; a.delta = delta;
+  a.seg_prefix = seg_prefix; a.seg_len = seg_len; a.use_tr = use_tr;
+  if (seq_meta) { a.seq_meta = seq_meta; a.meta_stride = meta_stride; a.n_seg = n_seg; a.rows_total = rows_total; }
+  a.rope_pos = rope_pos; a.rope_l2theta = rope_l2theta;
+  return opadpo_report_done(launch_attn_bwd(a, (hipStream_t)stream), fn);
 }

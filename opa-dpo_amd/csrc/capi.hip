@@ -21,6 +21,10 @@ inline int done(hipError_t e, const char* where) { return e == hipSuccess ? 0 : 
 inline hipStream_t S(void* s) { return (hipStream_t)s; }
 }  // namespace
 
+// the same reporting for extern "C" entry points that live in other translation units (kernels.h)
+int opadpo_report_bad(const char* where, const char* what) { return bad(where, what); }
+int opadpo_report_done(hipError_t e, const char* where) { return done(e, where); }
+
 extern "C" {
 
 int opadpo_abi_version(void) { return OPADPO_ABI_VERSION; }

@@ -98,6 +98,9 @@ struct GemmTNGroup {
 };
 
 void opadpo_set_flags_impl(int use_glds, int use_tr);
+// opadpo_last_error() reporting for entry points outside capi.hip: a message -> hipErrorInvalidValue; hipSuccess -> 0, else the code + its text
+int opadpo_report_bad(const char* where, const char* what);
+int opadpo_report_done(hipError_t e, const char* where);
 bool opadpo_flag_tr();
 void opadpo_set_attn_dma(bool on);
 

@@ -516,7 +516,7 @@ def test_attn_fwd(L, tr, S, Ln, nh, hd, causal, masked):
         allow = allow & km.bool()[:, None, None, :]
     want_lse = torch.logsumexp(sc.masked_fill(~allow, float("-inf")), -1)
     okr = allow.any(-1).expand(S, nh, Ln)
-    assert float((lse - want_lse)[okr].abs().max()) < 2e-2
+    assert float((lse - want_lse)[okr].abs().max()) < 1.9e-6        # worst over this test's grid on an MI355X: 9.54e-7
 
 
 @pytest.mark.parametrize("tr", [1, 0])
@@ -554,6 +554,15 @@ def test_attn_bwd(L, tr, S, Ln, nh, hd, masked):
                            ("dv", dqkv[:, 2 * H:], v4.grad.reshape(S * Ln, H))):
         e = relerr(got, ref)
         assert e < 2e-2, f"attn_bwd {name} rel err {e}"
+    # without the fp32 copy, as the model calls it (head_dim 128: the 32-rows-per-wave dQ kernel); dK / dV come from the same kernel
+    dqkv2 = torch.zeros(S * Ln, 3 * H, dtype=BF, device=dev())
+    L.call("opadpo_attn_bwd", qkv.data_ptr(), qkv.data_ptr() + 2 * H, qkv.data_ptr() + 4 * H, 3 * H, o.data_ptr(),
+           dout.data_ptr(), H, lse.data_ptr(), L.ptr(km), dqkv2.data_ptr(), dqkv2.data_ptr() + 2 * H,
+           dqkv2.data_ptr() + 4 * H, None, delta.data_ptr(), S, Ln, nh, hd, 1, scale, 0, 0, st)
+    torch.cuda.synchronize()
+    assert torch.equal(dqkv2[:, H:], dqkv[:, H:])
+    e = relerr(dqkv2[:, :H], q4.grad.reshape(S * Ln, H))
+    assert e < 2e-2, f"attn_bwd dq (no fp32 copy) rel err {e}"
 
 
 @pytest.mark.parametrize("tr", [1, 0, 3])
@@ -573,17 +582,17 @@ def test_attn_packed_responses(L, tr, S, nh, hd, pfx, T, K):
     km[-1, pfx + T - 5: pfx + T] = 0                   # right padding of response 0
     st = L.stream()
 
-    def run(x, do, mask, S_, L_, seg):
+    def run(x, do, mask, S_, L_, seg, copy=True):
         o = torch.zeros(S_ * L_, H, dtype=BF, device=dev())
         lse = torch.zeros(S_, nh, L_, device=dev())
         L.call("opadpo_attn_fwd", x.data_ptr(), x.data_ptr() + 2 * H, x.data_ptr() + 4 * H, 3 * H, o.data_ptr(), H,
                lse.data_ptr(), mask.data_ptr(), S_, L_, nh, hd, 1, scale, seg[0], seg[1], st)
         dx = torch.zeros(S_ * L_, 3 * H, dtype=BF, device=dev())
-        dq32 = torch.zeros(S_ * L_, H, device=dev())
+        dq32 = torch.zeros(S_ * L_, H, device=dev()) if copy else None
         delta = torch.zeros(S_, nh, L_, device=dev())
         L.call("opadpo_attn_bwd", x.data_ptr(), x.data_ptr() + 2 * H, x.data_ptr() + 4 * H, 3 * H, o.data_ptr(),
                do.data_ptr(), H, lse.data_ptr(), mask.data_ptr(), dx.data_ptr(), dx.data_ptr() + 2 * H, dx.data_ptr() + 4 * H,
-               dq32.data_ptr(), delta.data_ptr(), S_, L_, nh, hd, 1, scale, seg[0], seg[1], st)
+               L.ptr(dq32), delta.data_ptr(), S_, L_, nh, hd, 1, scale, seg[0], seg[1], st)
         torch.cuda.synchronize()
         return o, dx
 
@@ -597,6 +606,11 @@ def test_attn_packed_responses(L, tr, S, nh, hd, pfx, T, K):
     for name, got, ref in (("dq", dx[:, :H], q4.grad), ("dk", dx[:, H:2 * H], k4.grad), ("dv", dx[:, 2 * H:], v4.grad)):
         e = relerr(got, ref.reshape(S * Ln, H))
         assert e < 2e-2, f"packed attn_bwd {name} rel err {e}"
+    # without the fp32 dQ copy, as the model calls it: same dK / dV bits, dQ against the reference
+    _, dxn = run(qkv, dout, km, S, Ln, (pfx, T), copy=False)
+    assert torch.equal(dxn[:, H:], dx[:, H:])
+    e = relerr(dxn[:, :H], q4.grad.reshape(S * Ln, H))
+    assert e < 2e-2, f"packed attn_bwd dq (no fp32 copy) rel err {e}"
     # (b) the K separate sequences [prefix | response_k] (kernel without segments): same response outputs; the prefix
     # gradients of the packed row are the sum over the K sequences
     x3 = qkv.view(S, Ln, 3 * H)
