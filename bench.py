@@ -6,6 +6,12 @@ L = 1087 LLM positions), synthetic image+text batches, random-init weights of th
                                                            # torch.distributed.run (one rank per GPU, RCCL, rendezvous on 127.0.0.1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W     # same thing, launched from outside
     python bench.py --gpus 2 --dry-run                     # launcher + rendezvous + bucketed exchange self-check, no kernels (gloo on a CPU box)
+    python bench.py --gpus N --steps K --warmup W --full   # the same line plus every side record (see below)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if given and prints the line: the headline, the roofline of the
+timed steps (HIP events inside them) and the FLOP accounting.  `--full` adds what takes runs or reads of its own after the timed region:
+dense / unmerged-reference / unfused-epilogue steps, the exchange overlap and probe (N = 1) or the exposed exchange (N > 1), the CPU
+baseline, the rollout decode, the parity record, and the 13B and recipe configurations; each `--no-*` switch drops one of them again.
 
 One STEP = one optimizer step on every rank: `accum` (default 1) micro-batches of `pairs` (default 22) (image, chosen, rejected)
 pairs -> vision encode (once per image) -> frozen-reference forward (no grad) -> policy forward (activations
@@ -326,7 +332,7 @@ def rollout_leg(eng, d, dev, batches=(8, 64), steps=64):
 
 
 def extra_config(which):
-    """Sub-records of the default line for the BASELINE.json configurations the headline does not cover (measured AFTER the timed region,
+    """Sub-records of the --full line for the BASELINE.json configurations the headline does not cover (measured AFTER the timed region,
     in a child process on the same GPU; never part of `value`):
       thirteen_b : configs[3]'s model at 1 GPU - LLaVA-1.5-13B LoRA DPO, 12 packed pairs per step, 6 timed steps (this file, --model 13b);
       recipe     : the reference's NATIVE unit at the shipped recipe's lengths (run/train_opa_dpo.sh:39-50: query 128, response 896, 3 responses
@@ -619,6 +625,8 @@ def main():
     ap.add_argument("--accum", type=int, default=int(os.environ.get("OPADPO_BENCH_ACCUM", 1)), help="micro-batches per optimizer step")
     ap.add_argument("--model", default=os.environ.get("OPADPO_BENCH_MODEL", "7b"), choices=["7b", "13b", "tiny"])
     ap.add_argument("--optimizer-mode", default="zero1", choices=["allreduce", "zero1"])
+    ap.add_argument("--full", action="store_true", help="also measure every side record after the timed region (CPU baseline, other configurations, "
+                                                         "parity, rollout, exchange); a plain run measures only the headline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--batch-pool", type=int, default=8, help="number of different synthetic micro-batches cycled over the steps")
     ap.add_argument("--padded", action="store_true", help="keep the reference's padded rows (padding positions computed and thrown away) instead of ragged rows")
@@ -638,6 +646,8 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.dry_run:
         ap.error("--dump-outputs needs the real step; --dry-run runs no kernels")
+    if not args.full:      # a plain run: the headline alone, every side record off
+        args.no_cpu_baseline = args.no_rollout = args.no_side_legs = args.no_exchange_probe = args.no_extra_configs = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # no launcher environment: start the ranks ourselves (the driver calls `python bench.py --gpus N` the same way as for N = 1)
         if not args.dry_run and torch.cuda.device_count() < args.gpus and os.environ.get("OPADPO_BENCH_SHARE_DEVICE") != "1":
@@ -923,7 +933,7 @@ def main():
         if dist_rec is not None:
             check_dist_record(dist_rec, world, True)
             out["dist"] = dist_rec
-        if args.model == "7b" and (world > 1 or args.no_extra_configs):      # default N = 1 line: measured in this run, below (after the state is released)
+        if args.full and args.model == "7b" and (world > 1 or args.no_extra_configs):      # full N = 1 line: measured in this run, below (after the state is released)
             par = _parity_record()
             if par is not None:
                 out["parity"] = par

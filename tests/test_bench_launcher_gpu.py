@@ -25,7 +25,7 @@ def _run(*argv, share=False):
 @pytest.mark.parametrize("mode", ["zero1", "allreduce"])
 def test_bench_two_ranks_self_launched(mode):
     d, r = _run("--gpus", "2", "--model", "tiny", "--pairs", "4", "--steps", "2", "--warmup", "1", "--backend", "gloo",
-                "--optimizer-mode", mode, share=True)
+                "--optimizer-mode", mode, "--full", share=True)
     assert "launching 2 ranks" in r.stderr
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["config"]["global_pairs_per_step"] == 8
     assert abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-6
@@ -41,6 +41,21 @@ def test_bench_two_ranks_self_launched(mode):
 def test_bench_one_rank_line_has_no_dist_record():
     d, r = _run("--gpus", "1", "--model", "tiny", "--pairs", "4", "--steps", "2", "--warmup", "1", "--no-side-legs")
     assert "launching" not in r.stderr and "dist" not in d and d["n_gpus"] == 1 and d["value"] > 0
+
+
+SIDE_RECORDS = ("dense", "reference_unmerged", "unfused_epilogues", "exchange_overlap", "exchange_probe", "cpu_baseline", "rollout", "parity",
+                "thirteen_b", "recipe")
+
+
+def test_bench_plain_line_has_no_side_records_and_full_adds_them():
+    argv = ("--gpus", "1", "--model", "tiny", "--pairs", "4", "--steps", "2", "--warmup", "1")
+    d, _ = _run(*argv)
+    assert d["value"] > 0 and d["roofline"] is not None and d["roofline"]["achieved"] > 0
+    assert not [k for k in SIDE_RECORDS if k in d]
+    f, _ = _run(*argv, "--full")
+    for k in ("dense", "reference_unmerged", "unfused_epilogues"):      # the side legs of any model at N = 1 (the others are 7B-only)
+        assert k in f and "error" not in f[k], (k, f.get(k))
+        assert f[k]["ms_per_step"] > 0
 
 
 def test_bench_dump_outputs_repeat_with_the_same_arguments(tmp_path):

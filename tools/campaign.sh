@@ -13,7 +13,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   ( time python -m pytest tests/ -x -q -m gpu ) > $O/gpu_tests.log 2>&1
   tail -4 $O/gpu_tests.log
 fi
-python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err
 python -c "import json;r=json.load(open('$O/bench_default.json'));print('bench', r['value'], r['ms_per_step'], r['roofline']['frac'])"
 bash tools/prof.sh ${TAG}_bench python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-rollout --no-exchange-probe --no-side-legs > $O/prof.log 2>&1
 cp $R/gpurun_out/${TAG}_bench_kernel_stats.csv $O/bench_7b_kernel_stats.csv
