@@ -19,6 +19,41 @@ int bad(const char* where, const char* what) {
 }
 inline int done(hipError_t e, const char* where) { return e == hipSuccess ? 0 : fail(e, where); }
 inline hipStream_t S(void* s) { return (hipStream_t)s; }
+
+// opadpo_gemm_nt's validation and argument block
+int gemm_nt_args(GemmNTArgs& a, const char* fn, const uint16_t* A1, int lda1, const uint16_t* B1, int ldb1, int K1,
+                 const uint16_t* A2, int lda2, const uint16_t* B2, int ldb2, int K2, int a2_group_n, int a2_group_stride, int a1_group_n, int a1_group_stride,
+                 void* C, int ldc, int out_f32, const void* R, int ldr, int res_f32, const uint16_t* bias, int M, int N, float alpha, int act) {
+  if (M < 0 || N <= 0 || N % 128) return bad(fn, "N must be a positive multiple of 128");
+  if (K1 < 0 || K2 < 0 || K1 % 64 || K2 % 64 || K1 + K2 == 0) return bad(fn, "K1/K2 must be multiples of 64");
+  if ((K1 && (!A1 || !B1)) || (K2 && (!A2 || !B2)) || !C) return bad(fn, "null operand");
+  if (lda1 % 8 || ldb1 % 8 || (K2 && (lda2 % 8 || ldb2 % 8)) || ldc % 4 || (R && ldr % 4))
+    return bad(fn, "leading dimensions must keep 16-byte operand / 8-byte output alignment");
+  if ((a2_group_n && a2_group_n % 128) || (a1_group_n && a1_group_n % 128))
+    return bad(fn, "group widths must be multiples of the 128-column tile");
+  a.A1 = A1; a.B1 = B1; a.A2 = A2; a.B2 = B2; a.C = C; a.R = R; a.bias = bias;
+  a.M = M; a.N = N; a.K1 = K1; a.K2 = K2;
+  a.lda1 = lda1; a.ldb1 = ldb1; a.lda2 = lda2; a.ldb2 = ldb2; a.ldc = ldc; a.ldr = ldr;
+  a.a2_group_n = a2_group_n; a.a2_group_stride = a2_group_stride;
+  a.a1_group_n = a1_group_n; a.a1_group_stride = a1_group_stride;
+  a.alpha = alpha; a.act = act; a.out_f32 = out_f32; a.r_f32 = res_f32;
+  return 0;
+}
+
+// The op-level entries have no context: the K-folded products (gemm_nt_workspace_bytes) take their partial sums from one library-owned
+// buffer, used in stream order (grown on demand: a device-synchronising hipFree + hipMalloc, first steps only)
+hipError_t gemm_nt_op(const GemmNTArgs& a, hipStream_t st) {
+  static void* ws = nullptr;
+  static size_t ws_bytes = 0;
+  const size_t need = gemm_nt_workspace_bytes(a);
+  if (need > ws_bytes) {
+    if (ws) (void)hipFree(ws);
+    ws = nullptr; ws_bytes = 0;
+    if (hipMalloc(&ws, need + need / 4) != hipSuccess) { (void)hipGetLastError(); return hipErrorOutOfMemory; }
+    ws_bytes = need + need / 4;
+  }
+  return launch_gemm_nt(a, st, ws, ws_bytes);
+}
 }  // namespace
 
 // the same reporting for extern "C" entry points that live in other translation units (kernels.h)
@@ -36,21 +71,32 @@ int opadpo_gemm_nt(const uint16_t* A1, int lda1, const uint16_t* B1, int ldb1, i
                    int a2_group_n, int a2_group_stride, int a1_group_n, int a1_group_stride,
                    void* C, int ldc, int out_f32, const void* R, int ldr, int res_f32, const uint16_t* bias,
                    int M, int N, float alpha, int act, void* stream) {
-  if (M < 0 || N <= 0 || N % 128) return bad("opadpo_gemm_nt", "N must be a positive multiple of 128");
-  if (K1 < 0 || K2 < 0 || K1 % 64 || K2 % 64 || K1 + K2 == 0) return bad("opadpo_gemm_nt", "K1/K2 must be multiples of 64");
-  if ((K1 && (!A1 || !B1)) || (K2 && (!A2 || !B2)) || !C) return bad("opadpo_gemm_nt", "null operand");
-  if (lda1 % 8 || ldb1 % 8 || (K2 && (lda2 % 8 || ldb2 % 8)) || ldc % 4 || (R && ldr % 4))
-    return bad("opadpo_gemm_nt", "leading dimensions must keep 16-byte operand / 8-byte output alignment");
-  if ((a2_group_n && a2_group_n % 128) || (a1_group_n && a1_group_n % 128))
-    return bad("opadpo_gemm_nt", "group widths must be multiples of the 128-column tile");
   GemmNTArgs a;
-  a.A1 = A1; a.B1 = B1; a.A2 = A2; a.B2 = B2; a.C = C; a.R = R; a.bias = bias;
-  a.M = M; a.N = N; a.K1 = K1; a.K2 = K2;
-  a.lda1 = lda1; a.ldb1 = ldb1; a.lda2 = lda2; a.ldb2 = ldb2; a.ldc = ldc; a.ldr = ldr;
-  a.a2_group_n = a2_group_n; a.a2_group_stride = a2_group_stride;
-  a.a1_group_n = a1_group_n; a.a1_group_stride = a1_group_stride;
-  a.alpha = alpha; a.act = act; a.out_f32 = out_f32; a.r_f32 = res_f32;
-  return done(launch_gemm_nt(a, S(stream)), "opadpo_gemm_nt");
+  const int rc = gemm_nt_args(a, "opadpo_gemm_nt", A1, lda1, B1, ldb1, K1, A2, lda2, B2, ldb2, K2, a2_group_n, a2_group_stride, a1_group_n, a1_group_stride,
+                              C, ldc, out_f32, R, ldr, res_f32, bias, M, N, alpha, act);
+  return rc ? rc : done(gemm_nt_op(a, S(stream)), "opadpo_gemm_nt");
+}
+
+// test entry point (not in the public header): the launches opadpo_gemm_nt would make under opadpo_set_flags(gemm_variant, use_tr) on `cus` CUs,
+// as text (one line per launch: kernel grid.x grid.y block LDS); nothing is launched.  rope: 1 the table form of opadpo_gemm_nt_rope, 2 the table-free
+// form of opadpo_gemm_nt_rope_pos (both over all N columns; the operand pointers are never read)
+int opadpo_debug_gemm_nt_plan(const uint16_t* A1, int lda1, const uint16_t* B1, int ldb1, int K1,
+                              const uint16_t* A2, int lda2, const uint16_t* B2, int ldb2, int K2,
+                              int a2_group_n, int a2_group_stride, int a1_group_n, int a1_group_stride,
+                              void* C, int ldc, int out_f32, const void* R, int ldr, int res_f32, const uint16_t* bias,
+                              int M, int N, float alpha, int act, int gemm_variant, int use_tr, int rope, int cus, char* out, int out_len) {
+  GemmNTArgs a;
+  const char* fn = "opadpo_debug_gemm_nt_plan";
+  const int rc = gemm_nt_args(a, fn, A1, lda1, B1, ldb1, K1, A2, lda2, B2, ldb2, K2, a2_group_n, a2_group_stride, a1_group_n, a1_group_stride,
+                              C, ldc, out_f32, R, ldr, res_f32, bias, M, N, alpha, act);
+  if (rc) return rc;
+  if (!out || out_len <= 0 || cus <= 0 || rope < 0 || rope > 2) return bad(fn, "output buffer, CU count or rope selector");
+  static const float tab = 0.f;
+  static const int32_t pos = 0;
+  a.rope_cols = rope ? N : 0;
+  if (rope == 1) { a.rope_cos = &tab; a.rope_sin = &tab; a.rope_L = 4096; }
+  if (rope == 2) { a.rope_pos = &pos; a.rope_l2theta = log2f(10000.f); }
+  return done(gemm_nt_plan_text(a, gemm_variant, use_tr, cus, out, (size_t)out_len), fn);
 }
 
 int opadpo_gemm_nt_rope(const uint16_t* A1, int lda1, const uint16_t* B1, int ldb1, int K1,
@@ -71,7 +117,7 @@ int opadpo_gemm_nt_rope(const uint16_t* A1, int lda1, const uint16_t* B1, int ld
   a.a2_group_n = a2_group_n; a.a2_group_stride = a2_group_stride; a.a1_group_n = 0; a.a1_group_stride = 0;
   a.alpha = 1.0f; a.act = 0; a.out_f32 = 0; a.r_f32 = 0;
   a.rope_cos = cos_tab; a.rope_sin = sin_tab; a.rope_L = L; a.rope_cols = rope_cols; a.rope_seg_prefix = seg_prefix; a.rope_seg_len = seg_len;
-  return done(launch_gemm_nt(a, S(stream)), "opadpo_gemm_nt_rope");
+  return done(gemm_nt_op(a, S(stream)), "opadpo_gemm_nt_rope");
 }
 
 int opadpo_gemm_nt_rope_pos(const uint16_t* A1, int lda1, const uint16_t* B1, int ldb1, int K1,
@@ -90,7 +136,7 @@ int opadpo_gemm_nt_rope_pos(const uint16_t* A1, int lda1, const uint16_t* B1, in
   a.a2_group_n = a2_group_n; a.a2_group_stride = a2_group_stride; a.a1_group_n = 0; a.a1_group_stride = 0;
   a.alpha = 1.0f; a.act = 0; a.out_f32 = 0; a.r_f32 = 0;
   a.rope_pos = row_pos; a.rope_l2theta = log2f(theta); a.rope_cols = rope_cols;
-  return done(launch_gemm_nt(a, S(stream)), "opadpo_gemm_nt_rope_pos");
+  return done(gemm_nt_op(a, S(stream)), "opadpo_gemm_nt_rope_pos");
 }
 
 int opadpo_gemm_nt_decode(const uint16_t* A, int lda, const uint16_t* B, int ldb, int K, void* C, int ldc, int mode, int M, int N, int splits,

@@ -241,6 +241,7 @@ struct opadpo_ctx {
   struct Block { void* p; size_t bytes; };
   std::vector<Block> cache;                       // released arenas kept for reuse (default allocator only)
   void* ws = nullptr; size_t ws_bytes = 0;        // scratch of vision / backward / decode
+  void* gemm_ws = nullptr; size_t gemm_ws_bytes = 0;      // partial sums of the K-folded gemm_nt products (run_gemm; never c->ws, which passes carve around it)
   size_t bytes_live = 0, bytes_peak = 0;
   size_t arena_hint[2][16] = {};                  // largest activation arena requested so far, per (no-grad / training pass, responses per row K):
                                                   // CoPO's K = 2 masked pass does not inherit the K = 3 pass's worst case
@@ -311,14 +312,20 @@ void ctx_free(opadpo_ctx* c, void* p, size_t bytes) {
   if (c->alloc) c->dealloc(p, c->alloc_user);
   else c->cache.push_back({p, bytes});            // same-stream reuse is ordered; opadpo_ctx_trim() returns it to the driver
 }
-void* ctx_ws(opadpo_ctx* c, size_t bytes, hipStream_t st) {
-  if (bytes <= c->ws_bytes) return c->ws;
-  if (c->ws) { if (c->alloc) c->dealloc(c->ws, c->alloc_user); else (void)hipFree(c->ws); c->ws = nullptr; c->ws_bytes = 0; }
-  if (c->alloc) c->ws = c->alloc(bytes, (void*)st, c->alloc_user);
-  else if (hipMalloc(&c->ws, bytes) != hipSuccess) { (void)hipGetLastError(); c->ws = nullptr; }
-  c->ws_bytes = c->ws ? bytes : 0;
-  return c->ws;
+// a context-owned scratch buffer (c->ws, c->gemm_ws) of at least `bytes`: grown through the context allocator, contents not kept
+void ws_release(opadpo_ctx* c, void*& p, size_t& held) {
+  if (p) { if (c->alloc) c->dealloc(p, c->alloc_user); else (void)hipFree(p); }
+  p = nullptr; held = 0;
 }
+void* ws_grow(opadpo_ctx* c, void*& p, size_t& held, size_t bytes, hipStream_t st) {
+  if (bytes <= held) return p;
+  ws_release(c, p, held);
+  if (c->alloc) p = c->alloc(bytes, (void*)st, c->alloc_user);
+  else if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
+  held = p ? bytes : 0;
+  return p;
+}
+void* ctx_ws(opadpo_ctx* c, size_t bytes, hipStream_t st) { return ws_grow(c, c->ws, c->ws_bytes, bytes, st); }
 
 // bump carving of one arena
 struct Carve {
@@ -345,7 +352,9 @@ inline GemmNTArgs& resid(GemmNTArgs& a, const void* R, int ldr, int r_f32) { a.R
 // every gemm_nt launch of the context goes through here: with opadpo_ctx_profile(ctx, 1) each launch is bracketed by HIP events on
 // the launch stream (bench.py's live measurement of the dominant kernel: algorithmic FLOPs / measured duration)
 hipError_t run_gemm(opadpo_ctx* c, const GemmNTArgs& g, hipStream_t st) {
-  if (!c->prof) return launch_gemm_nt(g, st);
+  const size_t need = gemm_nt_workspace_bytes(g);
+  if (need > c->gemm_ws_bytes && !ws_grow(c, c->gemm_ws, c->gemm_ws_bytes, need + need / 4, st)) return hipErrorOutOfMemory;
+  if (!c->prof) return launch_gemm_nt(g, st, c->gemm_ws, c->gemm_ws_bytes);
   hipEvent_t e0, e1;
   hipError_t e;
   if (c->prof_pool.size() >= 2) {
@@ -356,7 +365,7 @@ hipError_t run_gemm(opadpo_ctx* c, const GemmNTArgs& g, hipStream_t st) {
     if ((e = hipEventCreate(&e1)) != hipSuccess) return e;
   }
   if ((e = hipEventRecord(e0, st)) != hipSuccess) return e;
-  e = launch_gemm_nt(g, st);
+  e = launch_gemm_nt(g, st, c->gemm_ws, c->gemm_ws_bytes);
   (void)hipEventRecord(e1, st);
   c->prof_ev.push_back({e0, e1});
   c->prof_flops.push_back(2.0 * (double)g.M * (double)g.N * (double)(g.K1 + g.K2));
@@ -632,7 +641,8 @@ void opadpo_ctx_destroy(opadpo_ctx* c) {
   opadpo_decode_end(c);
   while (!c->live.empty()) saved_destroy(c, c->live.back());
   for (auto& b : c->cache) (void)hipFree(b.p);
-  if (c->ws) { if (c->alloc) c->dealloc(c->ws, c->alloc_user); else (void)hipFree(c->ws); }
+  ws_release(c, c->ws, c->ws_bytes);
+  ws_release(c, c->gemm_ws, c->gemm_ws_bytes);
   if (c->rope_own) (void)hipFree(c->rope_own);
   for (auto& pr : c->prof_ev) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (auto& ev : c->prof_pool) (void)hipEventDestroy(ev);
@@ -647,7 +657,7 @@ const char* opadpo_ctx_last_error(const opadpo_ctx* c) { return c ? c->err.c_str
 int opadpo_ctx_set_allocator(opadpo_ctx* c, opadpo_alloc_fn alloc, opadpo_free_fn dealloc, void* user) {
   if (!c) return (int)hipErrorInvalidValue;
   if ((alloc == nullptr) != (dealloc == nullptr)) return cbad(c, __func__, "alloc and free must be given together");
-  if (c->bytes_live || c->ws) return cbad(c, __func__, "the allocator can only change while the context owns no memory");
+  if (c->bytes_live || c->ws || c->gemm_ws) return cbad(c, __func__, "the allocator can only change while the context owns no memory");
   for (auto& b : c->cache) (void)hipFree(b.p);
   c->cache.clear();
   c->alloc = alloc; c->dealloc = dealloc; c->alloc_user = user;
@@ -664,7 +674,8 @@ int opadpo_ctx_trim(opadpo_ctx* c) {
   if (!c) return (int)hipErrorInvalidValue;
   for (auto& b : c->cache) (void)hipFree(b.p);
   c->cache.clear();
-  if (c->ws) { if (c->alloc) c->dealloc(c->ws, c->alloc_user); else (void)hipFree(c->ws); c->ws = nullptr; c->ws_bytes = 0; }
+  ws_release(c, c->ws, c->ws_bytes);
+  ws_release(c, c->gemm_ws, c->gemm_ws_bytes);
   // the "largest activation arena seen so far" hints go too: after a trim the next pass sizes its arena for ITS batch shape (round 6: a 22-pair
   // training forward followed by a 2-pair one kept asking for the 22-pair arena - 155 GB at 7B - next to whatever else the host had allocated since)
   for (auto& row : c->arena_hint) for (auto& h : row) h = 0;

@@ -2263,36 +2263,39 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_kernel(GemmTNGroup G, int 
 }
 }  // namespace
 
-static bool g_skinny8 = true;       // M <= 16 decode GEMMs: whole-cache-line form of the streaming kernel
-static int g_dec64x_nw = 0;
-static int g_dec64_variant = getenv("OPADPO_DEC64_V") ? atoi(getenv("OPADPO_DEC64_V")) : 0;      // 0 / 3 the whole-line streaming kernel (dec64x), 1 the LDS-ring kernel; use_tr bits 5-6
-static int g_gemm_variant = 10;   // 10 (default): auto; 4: 128x128 kernel; 17: 8-wave 256x256 kernel (p8); 31: 4-wave 256x256 kernel (w4) forced; 15: M <= 64 streaming
-static bool g_use_tr = true;
-static int g_tn_w4 = 1;        // use_tr bit 3 CLEARS it: 256x256 gemm_tn_w4_kernel (default) vs the 128x128 kernel
-static bool g_w4s_few = false;      // opadpo_set_flags use_tr bit 10 (tests): 8 workgroups walk the tile list, so small problems exercise long walks
-static bool g_w4_chunk_deal = false; // opadpo_set_flags use_tr bit 12 (tests, A/B): every XCD walks a contiguous chunk of the tile order (rounds 1-5) instead of the block-cyclic deal
-static bool g_w4_nodeep = false;    // opadpo_set_flags use_tr bit 11 (tests, A/B): the products of >= 128 K-tiles keep the default K-loop text (round 6: they run the DEEP text)
-void opadpo_set_flags_impl(int use_glds, int use_tr) {
-  g_gemm_variant = use_glds;
-  g_use_tr = (use_tr & 1) != 0;
-  opadpo_set_attn_dma((use_tr & 2) != 0);
-  g_tn_w4 = (use_tr & 8) == 0;
-  g_skinny8 = (use_tr & 16) == 0;
-  if ((use_tr >> 5) & 3) g_dec64_variant = (use_tr >> 5) & 3; else if (!getenv("OPADPO_DEC64_V")) g_dec64_variant = 0;
-  opadpo_set_sample_compact((use_tr & 512) ? 0 : -1);      // bit 9 forces the diagnostic sampler; otherwise OPADPO_SAMPLE_COMPACT decides
-  g_w4s_few = (use_tr & 1024) != 0;
-  g_w4_nodeep = (use_tr & 2048) != 0;
-  g_w4_chunk_deal = (use_tr & 4096) != 0;
-  g_dec64x_nw = (use_tr >> 7) & 3;      // bits 7-8: rows per workgroup of the dec64x kernel (0 = by shape, 1 / 2 / 3 = 48 / 64 / 128; tests)
+// ---- process flags (opadpo_set_flags): one value, read by the dispatch of gemm_nt, gemm_tn and attention ------------------------------
+struct GemmFlags {
+  int variant = 10;             // gemm_variant: 10 (default) auto; 4: 128x128 kernel; 17: 8-wave 256x256 kernel (p8); 31: 4-wave 256x256 kernel (w4) forced; 15: M <= 64 streaming
+  bool use_tr = true;           // use_tr bit 0: transposed LDS reads
+  bool tn_w4 = true;            // bit 3 CLEARS it: 256x256 gemm_tn_w4_kernel (default) vs the 128x128 kernel
+  bool skinny8 = true;          // bit 4 CLEARS it: M <= 16 decode GEMMs: whole-cache-line form of the streaming kernel
+  int dec64_variant = 0;        // bits 5-6: 0 / 3 the whole-line streaming kernel (dec64x), 1 / 2 the LDS-ring kernel
+  int dec64x_nw = 0;            // bits 7-8: rows per workgroup of the dec64x kernel (0 = by shape, 1 / 2 / 3 = 48 / 64 / 128; tests)
+  bool w4s_few = false;         // bit 10 (tests): 8 workgroups walk the tile list, so small problems exercise long walks
+  bool w4_nodeep = false;       // bit 11 (tests, A/B): the products of >= 128 K-tiles keep the default K-loop text (round 6: they run the DEEP text)
+  bool w4_chunk_deal = false;   // bit 12 (tests, A/B): every XCD walks a contiguous chunk of the tile order (rounds 1-5) instead of the block-cyclic deal
+};
+static GemmFlags gemm_flags(int gemm_variant, int use_tr) {
+  GemmFlags f;
+  f.variant = gemm_variant;
+  f.use_tr = (use_tr & 1) != 0;
+  f.tn_w4 = (use_tr & 8) == 0;
+  f.skinny8 = (use_tr & 16) == 0;
+  f.dec64_variant = (use_tr >> 5) & 3;
+  f.dec64x_nw = (use_tr >> 7) & 3;
+  f.w4s_few = (use_tr & 1024) != 0;
+  f.w4_nodeep = (use_tr & 2048) != 0;
+  f.w4_chunk_deal = (use_tr & 4096) != 0;
+  return f;
 }
-bool opadpo_flag_tr() { return g_use_tr; }
+static GemmFlags g_flags;
+void opadpo_set_flags_impl(int use_glds, int use_tr) {
+  g_flags = gemm_flags(use_glds, use_tr);
+  opadpo_set_attn_dma((use_tr & 2) != 0);
+  opadpo_set_sample_compact((use_tr & 512) ? 0 : -1);      // bit 9 forces the diagnostic sampler; otherwise OPADPO_SAMPLE_COMPACT decides
+}
+bool opadpo_flag_tr() { return g_flags.use_tr; }
 
-// piece order of the 4-wave 256x256 kernel by shape (see gemm_nt_w4_kernel): B half first for N <= 16 column tiles
-static int g_w4_order = -1;      // OPADPO_W4_ORDER=0 / 1 forces A first / B first (experiments)
-// Streaming form (gemm_nt_w4s_kernel, round 5) for the plain products whenever every workgroup gets at least two tiles: one workgroup per CU walks
-// the tile list and keeps its K-tile pipeline full across output tiles.  OPADPO_W4S=0 / variant 31: one tile per workgroup (A/B, cross-check).
-static int g_w4s = -1, g_w4s_cus = 0, g_w4s_maxnt = 128;
-static const int env_rope_direct_ = getenv("OPADPO_ROPE_DIRECT") ? atoi(getenv("OPADPO_ROPE_DIRECT")) : 1;      // 0: table-free rotary embedding through the staged epilogue (rounds 3-4; A/B)
 // piece order of the 256x256 kernels: the B pieces of a K-tile first for <= 16 column tiles (o / down / the dgrads) and - under the block-cyclic deal, where the A panels
 // of a round are shared chip-wide - for the shallow products of up to 64 column tiles as well (q|k|v: +0.8-1.8 % at 7B, +0.9 % at 13B; the widest shapes lose 5-7 % with it:
 // profiles/r06zz_ab_order_cyclic.txt, r06zz_ab_order_other_shapes.txt); otherwise the A pieces first.  A placement choice: the results do not depend on it.
@@ -2300,46 +2303,6 @@ static bool w4_b_first(const GemmNTArgs& a) {
   const int tiles_n = a.N / P_BN, nt = (a.K1 + a.K2) / P_BK;
   return tiles_n <= 16 || (tiles_n <= 64 && nt < 128);
 }
-static const int env_w4_deep_ = getenv("OPADPO_W4_DEEP") ? atoi(getenv("OPADPO_W4_DEEP")) : 2;      // 2 (default): >= 128 K-tiles run the DEEP text, streaming where eligible; 1: DEEP text, one tile per workgroup; 0: default text (A/B)
-#define W4_LAUNCH(GRID_)                                                                                                     \
-  do {                                                                                                                       \
-    const bool ob_ = g_w4_order >= 0 ? g_w4_order != 0 : w4_b_first(a);                                                       \
-    const int grid_ = (GRID_), cus_ = g_w4s_few ? 8 : g_w4s_cus;                                                             \
-    const bool stream_ = g_w4s > 0 && g_gemm_variant != 31 && !a.bias && !a.rope_cos && !a.rope_pos && a.b1_fold_n == 0 &&                               \
-                         ((a.act == 0 && (!a.R || w4_direct_resid_ok(a))) || ((w4_direct_swiglu_bwd_ok(a) || w4_direct_swiglu_pair_ok(a)) && !a.swiglu_bwd_staged)) && \
-                         a.K1 / P_BK >= 3 && (a.K1 + a.K2) / P_BK <= g_w4s_maxnt && grid_ >= 2 * cus_;                              \
-    const bool deep_stream_ = env_w4_deep_ >= 2 && !g_w4_nodeep && g_w4s > 0 && g_gemm_variant != 31 && !a.bias && !a.rope_cos && !a.rope_pos && a.b1_fold_n == 0 && \
-                              a.act == 0 && (!a.R || w4_direct_resid_ok(a)) && a.K1 / P_BK >= 3 && (a.K1 + a.K2) / P_BK >= 128 && (a.K1 + a.K2) / P_BK > g_w4s_maxnt && \
-                              grid_ >= 2 * cus_;                                                                                \
-    if (g_w4s > 0 && g_gemm_variant != 31 && env_rope_direct_ && w4_direct_rope_pos_ok(a) && a.K1 / P_BK >= 3 && (a.K1 + a.K2) / P_BK <= g_w4s_maxnt && grid_ >= 2 * cus_) { \
-      if (ob_) hipLaunchKernelGGL((gemm_nt_w4s_kernel<true, 3>), dim3(cus_), dim3(256), 2 * P_STAGE, st, a, grid_);           \
-      else hipLaunchKernelGGL((gemm_nt_w4s_kernel<false, 3>), dim3(cus_), dim3(256), 2 * P_STAGE, st, a, grid_);              \
-    } else if (stream_ && a.act == OPADPO_ACT_SWIGLU_PAIR) {                                                                 \
-      if (ob_) hipLaunchKernelGGL((gemm_nt_w4s_kernel<true, 2>), dim3(cus_), dim3(256), 2 * P_STAGE, st, a, grid_);           \
-      else hipLaunchKernelGGL((gemm_nt_w4s_kernel<false, 2>), dim3(cus_), dim3(256), 2 * P_STAGE, st, a, grid_);              \
-    } else if (stream_) {                                                                                                    \
-      if (ob_) hipLaunchKernelGGL(gemm_nt_w4s_kernel<true>, dim3(cus_), dim3(256), 2 * P_STAGE, st, a, grid_);                \
-      else hipLaunchKernelGGL(gemm_nt_w4s_kernel<false>, dim3(cus_), dim3(256), 2 * P_STAGE, st, a, grid_);                   \
-    } else if (deep_stream_) {      /* >= 128 K-tiles: streaming pays with the DEEP text only (default text: -4.7 %) */      \
-      if (ob_) hipLaunchKernelGGL((gemm_nt_w4s_kernel<true, 0, true>), dim3(cus_), dim3(256), 2 * P_STAGE, st, a, grid_);     \
-      else hipLaunchKernelGGL((gemm_nt_w4s_kernel<false, 0, true>), dim3(cus_), dim3(256), 2 * P_STAGE, st, a, grid_);        \
-    }                                                                                                                        \
-    else if (env_w4_deep_ && !g_w4_nodeep && (a.K1 + a.K2) / P_BK >= 128) {      /* the deep-K products (down, the dgrads): the DEEP text */         \
-      if (ob_) hipLaunchKernelGGL((gemm_nt_w4_kernel<true, false, true>), dim3(grid_), dim3(256), 2 * P_STAGE, st, a);       \
-      else hipLaunchKernelGGL((gemm_nt_w4_kernel<false, false, true>), dim3(grid_), dim3(256), 2 * P_STAGE, st, a);          \
-    }                                                                                                                        \
-    else if (ob_) hipLaunchKernelGGL(gemm_nt_w4_kernel<true>, dim3(grid_), dim3(256), 2 * P_STAGE, st, a);                   \
-    else hipLaunchKernelGGL(gemm_nt_w4_kernel<false>, dim3(grid_), dim3(256), 2 * P_STAGE, st, a);                            \
-  } while (0)
-
-// the bias / activation instantiations (w4_direct_ba_ok problems: the vision tower and the projector): one tile per workgroup only - the streaming
-// kernel has no registers left for the bias / activation epilogue (it spills, and a kernel whose K-loop is an asm block must not touch scratch)
-#define W4_LAUNCH_BA(GRID_)                                                                                                  \
-  do {                                                                                                                       \
-    const bool ob_ = g_w4_order >= 0 ? g_w4_order != 0 : a.N / P_BN <= 16;                                                    \
-    if (ob_) hipLaunchKernelGGL((gemm_nt_w4_kernel<true, true>), dim3(GRID_), dim3(256), 2 * P_STAGE, st, a);                \
-    else hipLaunchKernelGGL((gemm_nt_w4_kernel<false, true>), dim3(GRID_), dim3(256), 2 * P_STAGE, st, a);                   \
-  } while (0)
 
 // ---- K-folded r-wide products (round 6) ---------------------------------------------------------------------------------------------
 // The N = lora_r = 256 products of the LoRA path (t = s x A^T for the o / down projections, dT = s dY B for their dgrads: four per layer and pass) are ONE
@@ -2361,241 +2324,16 @@ __global__ __launch_bounds__(256) void gemm_fold2_reduce_kernel(const float* __r
   *(uint4*)(C + (size_t)m * ldc + c) = pack8(v);
 }
 }  // namespace
-static float* g_fold_ws = nullptr;
-static size_t g_fold_ws_bytes = 0;      // one buffer per process = per GPU, used in stream order (grown on demand: a device-synchronising hipFree + hipMalloc, first steps only)
 static bool gemm_nt_kfold_ok(const GemmNTArgs& a, int variant) {
-  static const int env_fold = getenv("OPADPO_KFOLD") ? atoi(getenv("OPADPO_KFOLD")) : 1;      // 0: the r-wide products in one pass over K (rounds 1-5; A/B)
-  return env_fold && (variant == 10 || variant == 31) && !(a.act & OPADPO_GEMM_STREAM) && (a.act & 0xff) == 0 && a.N == 256 && a.K2 == 0 && !a.bias && !a.R &&
+  return (variant == 10 || variant == 31) && !(a.act & OPADPO_GEMM_STREAM) && (a.act & 0xff) == 0 && a.N == 256 && a.K2 == 0 && !a.bias && !a.R &&
          !a.out_f32 && !a.rope_cos && !a.rope_pos && a.a1_group_n <= 0 && a.b1_fold_n == 0 && !a.quarter && a.K1 % 128 == 0 && a.K1 >= 1024 && a.ldc % 8 == 0 &&
          a.lda1 % 8 == 0 && a.ldb1 % 8 == 0 && (double)a.M * a.lda1 * 2 < 4.0e9 && (double)a.N * a.ldb1 * 2 < 4.0e9 && (double)(a.M + 256) * 512 * 4 < 4.0e9;
 }
-
-hipError_t launch_gemm_nt(const GemmNTArgs& a_in, hipStream_t st) {
-  if (a_in.M <= 0) return hipSuccess;
-  if (gemm_nt_kfold_ok(a_in, a_in.variant >= 0 ? a_in.variant : ::g_gemm_variant)) {
-    const size_t need = (size_t)a_in.M * 512 * sizeof(float);
-    if (need > g_fold_ws_bytes) {
-      if (g_fold_ws) (void)hipFree(g_fold_ws);
-      g_fold_ws = nullptr; g_fold_ws_bytes = 0;
-      const size_t want = need + need / 4;
-      if (hipMalloc(&g_fold_ws, want) != hipSuccess) { (void)hipGetLastError(); return hipErrorOutOfMemory; }
-      g_fold_ws_bytes = want;
-    }
-    GemmNTArgs f = a_in;
-    f.N = 512; f.K1 = a_in.K1 / 2; f.a1_group_n = 256; f.a1_group_stride = a_in.K1 / 2; f.b1_fold_n = 256; f.b1_fold_koff = a_in.K1 / 2;
-    f.C = g_fold_ws; f.ldc = 512; f.out_f32 = 1; f.alpha = 1.0f;
-    hipError_t e = launch_gemm_nt(f, st);
-    if (e != hipSuccess) return e;
-    const size_t n = (size_t)a_in.M * (256 / 8);
-    hipLaunchKernelGGL(gemm_fold2_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g_fold_ws, (bf16_t*)a_in.C, a_in.ldc, a_in.M, 256, a_in.alpha);
-    return hipGetLastError();
-  }
-  GemmNTArgs a = a_in;
-  if (g_w4_order == -1) { const char* v = getenv("OPADPO_W4_ORDER"); g_w4_order = v ? atoi(v) : -2; }
-  // C leaves the 4-wave 256x256 kernel's direct epilogue as NON-TEMPORAL stores (round 4): at the end of a round all 256 workgroups write
-  // their 128-256 KiB of results at once - a 32-64 MB burst that drains at the fabric's write rate (the no-store diagnostic of the
-  // persistent-loop experiment put it at 4-5 us of a ~100 us tile) while nothing computes; streaming stores do not fight the operand
-  // panels for the 4-MiB L2s.  Same-box sustained A/B at M = 24576 (tools/ab_env.sh, profiles/r04_ab_nt_stores.txt): q|k|v +0.9 %, o
-  // (fp32 out) +2.5 %, gate|up +0.6 %, down (fp32 out) +1.0 %, N = 768 +1.2 %.  OPADPO_W4_NT=0 keeps write-back stores (A/B).
-  static const int env_nt = getenv("OPADPO_W4_NT") ? atoi(getenv("OPADPO_W4_NT")) : 1;
-  a.store_nt = env_nt;
-  // grouped tile order of the 256x256 4-wave kernel: 8 row tiles per group; 4 when the problem is at most 16 column tiles wide
-  // (N <= 4096: o / down and three of the four dgrads) - measured at M = 32362: down 1.363 -> 1.397 PF/s, o 1.394 -> 1.401,
-  // the wide projections lose 0.4-2 % with 4 or 6 and 6 % with 12.  OPADPO_W4_GM overrides (diagnostics).
-  static const int env_gm = getenv("OPADPO_W4_GM") ? atoi(getenv("OPADPO_W4_GM")) : 0;
-  a.group_m = env_gm > 0 ? env_gm : (a.N / P_BN <= 16 ? 4 : 8);
-  // 32-tile blocks dealt to the XCDs block-cyclically (round 6; common.h xcd_remap_cyclic): the eight XCDs of a round share one row group's A panels through the
-  // Infinity Cache and B stays within its reach between passes - down +2.0-5.3 %, gate|up +2.2-2.5 %, dgrad_gu +0.6-2.5 %, q|k|v +0.8-1.3 %, o +-0.2 %, step -1.0 %
-  // (profiles/r06z_ab_cyclic.txt).  OPADPO_XCD_CYCLIC=0 / opadpo_set_flags use_tr bit 12: the contiguous-chunk deal of rounds 1-5 (same results, bit for bit).
-  static const int env_cyc = getenv("OPADPO_XCD_CYCLIC") ? atoi(getenv("OPADPO_XCD_CYCLIC")) : 1;
-  a.xcd_cyclic = env_cyc && !g_w4_chunk_deal;
-  const bool stream_hint = (a.act & OPADPO_GEMM_STREAM) != 0;
-  a.act &= 0xff;
-  const int g_gemm_variant = a.variant >= 0 ? a.variant : ::g_gemm_variant;      // per-call override (opadpo_ctx_set_flags)
-  if (a.N % BN || a.K1 % BK || a.K2 % BK || a.K1 + a.K2 <= 0) return hipErrorInvalidValue;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel_x<64, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4s_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4s_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4s_kernel<false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4s_kernel<true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4s_kernel<false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4s_kernel<true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4s_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4s_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_w4_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    {
-      int dev_ = 0; hipDeviceProp_t pr_;
-      g_w4s_cus = (hipGetDevice(&dev_) == hipSuccess && hipGetDeviceProperties(&pr_, dev_) == hipSuccess) ? pr_.multiProcessorCount : 256;
-      g_w4s = getenv("OPADPO_W4S") ? atoi(getenv("OPADPO_W4S")) : 1;
-      if (getenv("OPADPO_W4S_MAXNT")) g_w4s_maxnt = atoi(getenv("OPADPO_W4S_MAXNT"));
-    }
-    (void)hipFuncSetAttribute((const void*)gemm_nt_tail64_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 16384);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_tail64_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 16384);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_p8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    attr_set = true;
-  }
-  if (a.b1_fold_n > 0) {      // K-folded problem (built above): every tile on gemm_nt_w4_kernel, the only kernel that reads the folded B1
-    if (a.N % P_BN || a.K1 % P_BK || a.K2) return hipErrorInvalidValue;
-    const int tiles = ((a.M + P_BM - 1) / P_BM) * (a.N / P_BN);
-    W4_LAUNCH(tiles);
-    return hipGetLastError();
-  }
-  // Decode-sized weight streams with nothing fused (no LoRA tail, bias, residual or scale; plain or SwiGLU-pair epilogue) go to the whole-line
-  // streaming kernel behind opadpo_gemm_nt_decode from 8 token rows up: the rollout's q|k|v, gate|up and lm_head at 8 sequences (decode step
-  // 3.79 -> 3.71 ms) and the lm_head at 9-64 (B=16: 4.42 -> 4.30 ms).  Below 8 rows the 8-row kernels are ahead in the step (B=5: 3.73 vs 3.86 ms,
-  // B=4: 3.41 vs 3.52; profiles/r04_decode_stream.txt section 16), and the projections with a residual epilogue (o, down) stay on them too.
-  // OPADPO_STREAM_DEC64X = fewest token rows routed (default 8; 0 = never).
-  static const int route_x = getenv("OPADPO_STREAM_DEC64X") ? atoi(getenv("OPADPO_STREAM_DEC64X")) : 8;
-  if (route_x > 0 && a.M >= route_x && stream_hint && g_gemm_variant == 10 && g_dec64_variant != 1 && a.M <= 64 && a.K2 == 0 && !a.bias && !a.R && a.alpha == 1.0f &&
-      a.a1_group_n <= 0 && !a.rope_cos && !a.rope_pos && a.K1 % 64 == 0 && a.N % 128 == 0 && a.lda1 % 8 == 0 && a.ldb1 % 8 == 0 && a.ldc % 4 == 0 &&
-      (a.act == 0 || (a.act == OPADPO_ACT_SWIGLU_PAIR && !a.out_f32)) && (double)a.M * a.lda1 * 2 < 4.0e9 && (double)a.N * a.ldb1 * 2 < 4.0e9) {
-    GemmNTArgs d = a;
-    const int mode = a.act == OPADPO_ACT_SWIGLU_PAIR ? 2 : a.out_f32 ? 1 : 0;
-    d.act = 0;
-    return launch_gemm_nt_dec64(d, mode, 1, st);
-  }
-  if (a.rope_cos || a.rope_pos) {      // fused rotary embedding: only the 4-wave 256x256 kernel implements it (bf16 out, alpha-only epilogue)
-    const bool ok32 = (double)a.M * a.lda1 * 2 < 4.0e9 && (double)a.N * a.ldb1 * 2 < 4.0e9 &&
-                      (a.K2 == 0 || ((double)a.M * a.lda2 * 2 < 4.0e9 && (double)a.N * a.ldb2 * 2 < 4.0e9));
-    if (a.bias || a.act || a.R || a.out_f32 || a.N % P_BN || !ok32 || a.rope_cols % 128) return hipErrorInvalidValue;
-    if (a.rope_cos && (a.rope_L < 4 || (a.rope_seg_len > 0 && a.rope_seg_len < 4))) return hipErrorInvalidValue;
-    if (a.rope_pos && !(a.rope_l2theta > 0.f)) return hipErrorInvalidValue;
-    const int tiles = ((a.M + P_BM - 1) / P_BM) * (a.N / P_BN);
-    W4_LAUNCH(tiles);
-    return hipGetLastError();
-  }
-  if (a.act == OPADPO_ACT_SWIGLU_BWD) {       // fused SwiGLU backward epilogue (R = stored [gate | up], C = [d_gate | d_up]): the 4-wave 256x256 kernel only
-    const bool ok32 = (double)a.M * a.lda1 * 2 < 4.0e9 && (double)a.N * a.ldb1 * 2 < 4.0e9 &&
-                      (a.K2 == 0 || ((double)a.M * a.lda2 * 2 < 4.0e9 && (double)a.N * a.ldb2 * 2 < 4.0e9));
-    if (a.bias || !a.R || a.r_f32 || a.out_f32 || a.alpha != 1.0f || a.N % P_BN || !ok32 || a.ldr % 8 || a.ldc % 8 || a.rope_cos) return hipErrorInvalidValue;
-    const int tiles = ((a.M + P_BM - 1) / P_BM) * (a.N / P_BN);
-    W4_LAUNCH(tiles);
-    return hipGetLastError();
-  }
-  if (a.act == OPADPO_ACT_SWIGLU_PAIR) {      // fused SwiGLU epilogue: the 4-wave 256x256 kernel, or the weight-streaming kernel for decode
-    const bool ok32 = (double)a.M * a.lda1 * 2 < 4.0e9 && (double)a.N * a.ldb1 * 2 < 4.0e9;
-    if (a.bias || a.R || a.out_f32 || a.alpha != 1.0f || a.K2 != 0 || a.N % P_BN || !ok32) return hipErrorInvalidValue;
-    if (a.M <= 64 && ((stream_hint && g_gemm_variant == 10) || g_gemm_variant == 15) && a.a1_group_n <= 0 && a.K1 % 32 == 0) {
-      const int mf = (a.M + 15) / 16;
-      const dim3 bl(512), gr(a.N / 32);
-      if (g_skinny8 && (a.M <= 16 || (a.M <= 32 && a.N / 32 < 512))) {       // same kernel family as the plain projection of this size
-        if (a.M <= 8) hipLaunchKernelGGL((gemm_nt_skinny8_kernel<1, 2, 8, true>), dim3(a.N / 16), bl, 0, st, a);
-        else if (a.M <= 16) hipLaunchKernelGGL((gemm_nt_skinny8_kernel<2, 2, 4, true>), dim3(a.N / 16), bl, 0, st, a);
-        else if (a.M <= 24) hipLaunchKernelGGL((gemm_nt_skinny8_kernel<3, 2, 2, true>), dim3(a.N / 16), bl, 0, st, a);
-        else hipLaunchKernelGGL((gemm_nt_skinny8_kernel<4, 2, 2, true>), dim3(a.N / 16), bl, 0, st, a);
-        return hipGetLastError();
-      }
-      if (mf == 1) hipLaunchKernelGGL((gemm_nt_skinny_kernel<1, 2, 8, true>), gr, bl, 0, st, a);
-      else if (mf == 2) hipLaunchKernelGGL((gemm_nt_skinny_kernel<2, 2, 4, true>), gr, bl, 0, st, a);
-      else if (mf == 3) hipLaunchKernelGGL((gemm_nt_skinny_kernel<3, 2, 2, true>), gr, bl, 0, st, a);
-      else hipLaunchKernelGGL((gemm_nt_skinny_kernel<4, 2, 2, true>), gr, bl, 0, st, a);
-      return hipGetLastError();
-    }
-    const int tiles = ((a.M + P_BM - 1) / P_BM) * (a.N / P_BN);
-    W4_LAUNCH(tiles);
-    return hipGetLastError();
-  }
-  // decode-sized problems (M <= 64): weight-streaming kernel, one workgroup per 16 (or 32) weight rows
-  if (a.M <= 64 && ((stream_hint && g_gemm_variant == 10) || g_gemm_variant == 15)) {
-    const int mf = (a.M + 15) / 16;
-    // 32 weight rows per workgroup halve the activation re-reads from L2 (they bound the kernel from M ~ 32 on) but also the
-    // number of blocks: measured better only while >= 384 blocks remain (N = 4096 at 128 blocks: 29 vs 24 us at M = 64)
-    const bool wide = a.N % 32 == 0 && a.N / 32 >= (mf >= 3 ? 384 : 512) && (a.a1_group_n <= 0 || a.a1_group_n % 32 == 0) &&
-                      (a.a2_group_n <= 0 || a.a2_group_n % 32 == 0);
-    const dim3 bl(512), gr(wide ? a.N / 32 : a.N / 16);
-#define SK(MF_, NR_, U_) hipLaunchKernelGGL((gemm_nt_skinny_kernel<MF_, NR_, U_>), gr, bl, 0, st, a)
-    if (g_skinny8 && a.M > 16 && a.M <= 32 && !wide && (a.a1_group_n <= 0 || a.a1_group_n % 16 == 0) && (a.a2_group_n <= 0 || a.a2_group_n % 16 == 0)) {
-      // 17..32 tokens, narrow N (q|k|v, o, down at 7B): the whole-cache-line form still wins (M = 24: 37 -> 31, 15 -> 13, 37 -> 28 us);
-      // the 32-row form above keeps the wide projections (activation re-reads from L2 dominate there)
-      if (a.M <= 24) hipLaunchKernelGGL((gemm_nt_skinny8_kernel<3, 2, 2>), dim3(a.N / 16), bl, 0, st, a);
-      else hipLaunchKernelGGL((gemm_nt_skinny8_kernel<4, 2, 2>), dim3(a.N / 16), bl, 0, st, a);
-      return hipGetLastError();
-    }
-    if (g_skinny8 && a.M <= 16 && (a.a1_group_n <= 0 || a.a1_group_n % 32 == 0) && (a.a2_group_n <= 0 || a.a2_group_n % 32 == 0)) {
-      const bool wide8 = a.N % 32 == 0 && a.N / 32 >= 512;          // 32 weight rows per workgroup while >= 2 rounds of blocks remain
-#define SK8(MF8_, NR_, U_) hipLaunchKernelGGL((gemm_nt_skinny8_kernel<MF8_, NR_, U_>), dim3(a.N / (8 * NR_)), bl, 0, st, a)
-      if (a.M <= 8) { if (wide8) SK8(1, 4, 4); else SK8(1, 2, 8); }
-      else          { if (wide8) SK8(2, 4, 2); else SK8(2, 2, 4); }
-#undef SK8
-      return hipGetLastError();
-    }
-    if (wide) { if (mf == 1) SK(1, 2, 8); else if (mf == 2) SK(2, 2, 4); else if (mf == 3) SK(3, 2, 2); else SK(4, 2, 2); }
-    else      { if (mf == 1) SK(1, 1, 8); else if (mf == 2) SK(2, 1, 4); else if (mf == 3) SK(3, 1, 4); else SK(4, 1, 4); }
-#undef SK
-    return hipGetLastError();
-  }
-  // variant 10 (default, "auto"): a 256x256 kernel when it yields at least ~1.25 rounds of blocks on the 256 CUs (or fills its
-  // last round), the 128x128 kernel otherwise (skinny LoRA GEMMs, N not a multiple of 256).
-  const bool off32 = (double)a.M * a.lda1 * 2 < 4.0e9 && (double)a.N * a.ldb1 * 2 < 4.0e9 &&
-                     (a.K2 == 0 || ((double)a.M * a.lda2 * 2 < 4.0e9 && (double)a.N * a.ldb2 * 2 < 4.0e9));   // buffer offsets are 32-bit
-  const int pp_tiles = (a.N % P_BN == 0 && off32) ? ((a.M + P_BM - 1) / P_BM) * (a.N / P_BN) : 0;
-  // one 256x256 block per CU and round: below 1.25 rounds the big tile only pays when its last round fills the chip
-  // (M = 32362: N = 512 -> 254 blocks, w4 1.10-1.18 PF/s vs 0.75-0.79 for the 128x128 kernel; N = 768 -> 381 blocks = 1.49
-  // rounds, w4 1.10 vs 0.84; N = 256 -> 127 blocks, the 128x128 kernel wins 0.77 vs 0.63)
-  // the 4-wave kernels' hot instantiations take alpha-only epilogues; bias / quick-GELU / GELU problems (+ an fp32 residual into an fp32 result) run on
-  // their BA instantiations (round 5: the vision tower's and the projector's GEMMs left the 8-wave kernel / the 128x128 kernel for them)
-  static const int env_ba = getenv("OPADPO_W4_BA") ? atoi(getenv("OPADPO_W4_BA")) : 1;
-  const bool ba = env_ba && (g_gemm_variant == 10 || g_gemm_variant == 31) && w4_direct_ba_ok(a) && a.N % P_BN == 0 && off32 &&
-                  (double)(a.M + 256) * a.ldc * (a.out_f32 ? 4 : 2) < 4.0e9;
-  const bool plain = (!a.bias && !a.act) || ba;
-  const int pp_slots = ((pp_tiles + 255) / 256) * 256;
-  // ragged rows (M ~ 24-26 k): N = 512 -> 188-200 blocks in ONE round, w4 0.088 / 0.256 ms (K = 4096 / 11008) vs 0.121 / 0.424 for the
-  // 128x128 kernel; N = 768 -> 282-300 blocks: a tie; N = 256 -> 94-100 blocks: the 128x128 kernel keeps a 5-20 % lead
-  // with the quarter-tile tail (below) a second, short round costs 0.5-0.6 of a round: N = 768 (282-300 blocks) moves to the 256x256 kernel as
-  // well, and a deep-K one-round problem of <= 128 tiles (x . A_d^T: N = 256, K = 11008) runs as quarter tiles entirely (4x the blocks)
-  const int pp_rem = pp_tiles % 256, pp_nt = (a.K1 + a.K2) / P_BK;
-  const bool deep_small = plain && pp_tiles >= 64 && pp_tiles <= 128 && pp_nt >= 128;      // K = 4096 one-round problems measured no gain (0.085 vs 0.081 ms)
-  const bool big = g_gemm_variant == 17 || g_gemm_variant == 31 || (g_w4s_few && g_gemm_variant == 10 && plain && pp_tiles >= 16) ||      // (test switch: small problems stream on 8 workgroups)
-                   (g_gemm_variant != 4 && (pp_tiles >= 320 || (plain && pp_tiles >= 150 && (pp_tiles <= 256 || pp_rem <= 128)) || deep_small ||
-                                            (plain && pp_tiles >= 200 && pp_tiles * 100 >= pp_slots * 88)));
-  if (big && pp_tiles > 0) {
-    if (plain && g_gemm_variant != 17) {    // 4 waves x 128x128, long-lead DMA schedule, M0 one MFMA ahead of each DMA
-      const int full = pp_tiles / 256 * 256, rem = pp_tiles - full;
-      // a partly filled last round (<= 64 tiles) runs as QUARTER tiles on the 128x128 kernel - 4 blocks per 256x256 tile, each over the
-      // FULL K range in the same k order, so every element of C is bit-identical to what the 256x256 kernel writes and the result of a row
-      // does not depend on how many rows share the batch (WHICH tiles are tail tiles depends on M).
-      // (a deep-K problem of <= 128 tiles - x . A_d^T: N = 256, K = 11008 - runs as quarter tiles entirely: 4x the blocks on a chip it
-      // would fill to a third; variant 31 = the 256x256 kernel on every tile, the bit-for-bit cross-check of the tests).
-      // Measured (GB_ONLY=tail, N = 4096): a 16- or 64-tile tail costs 0.5-0.6 of a round as quarter tiles, a 128-tile tail 1.1-1.3 rounds
-      // (two quarter blocks share a CU there) - more than the plain partly filled round: quarter tiles up to 64 tiles only.
-      // Round 2's split-K tail (2 / 4 / 8 K-slices per tail tile + a reduce launch, a process-global fp32 workspace) was 1.1 % faster per step
-      // (964.4 vs 975.2 ms; no tail handling: 982.8) but re-associated the fp32 sums of the tail tiles, i.e. made a row's result depend on
-      // the batch's row count; removed.
-      if (g_gemm_variant != 31 && (full > 0 || deep_small) && rem > 0 && rem <= (deep_small && full == 0 ? 128 : 64)) {
-        if (full > 0) { if (ba) W4_LAUNCH_BA(full); else W4_LAUNCH(full); }
-        GemmNTArgs t = a;
-        t.quarter = 1; t.tile0 = full;
-        // (a four-stage ring for these blocks - three K-tiles in flight, one block per CU - measured 973.1 vs 969.9 ms per step: no gain,
-        // a lone 4-wave 128x128 block runs at ~0.6 PF/s per CU whatever its prefetch depth; removed)
-        // (round 4) tails of a multi-round launch run as SIXTEENTH tiles (16 blocks of 64x64 per tile: a 16-tile tail already fills the chip);
-        // the deep-K one-round problem keeps its quarter tiles (every tile of it is a "tail" tile: rate matters there).  OPADPO_TAIL16=0: quarter tiles
-        // Measured (GB_ONLY=tail, N = 4096; quarter tiles -> sixteenth tiles): 16-tile tail +38 -> +24 us (K = 4096), +115 -> +44 us (K = 11008);
-        // 32 tiles +51 -> +34, +115 -> +82; 48 tiles: a tie; 64 tiles (1024 blocks, four per CU): +50 -> +65, i.e. quarter tiles from 48 tiles on.
-        static const int tail16 = getenv("OPADPO_TAIL16") ? atoi(getenv("OPADPO_TAIL16")) : 1;
-        if (full > 0 && tail16 && rem <= 40) {
-          if (rem <= 16) hipLaunchKernelGGL(gemm_nt_tail64_kernel<8>, dim3(rem * 16), dim3(256), 8 * 16384, st, t);
-          else hipLaunchKernelGGL(gemm_nt_tail64_kernel<4>, dim3(rem * 16), dim3(256), 4 * 16384, st, t);
-        }
-        else hipLaunchKernelGGL((gemm_nt_kernel_x<64, true, 2>), dim3(rem * 4), dim3(256), 65536, st, t);
-        return hipGetLastError();
-      }
-      if (ba) W4_LAUNCH_BA(pp_tiles); else W4_LAUNCH(pp_tiles);
-    }
-    else                                    // bias / activation epilogues (vision tower, projector): 8 waves x 128x64, 4 phases per K-tile
-      hipLaunchKernelGGL(gemm_nt_p8_kernel, dim3(pp_tiles), dim3(512), 2 * P_STAGE, st, a);
-    return hipGetLastError();
-  }
-  const int tiles_x = ((a.M + BM - 1) / BM) * (a.N / BN);      // everything else (and variant 4): the 128x128 kernel
-  hipLaunchKernelGGL((gemm_nt_kernel_x<64, true, 2>), dim3(tiles_x), dim3(256), 65536, st, a);
-  return hipGetLastError();
+// fp32 partial products of a K-folded problem: [M, 2 x 256], in the caller's workspace (used in stream order)
+static size_t gemm_nt_fold_bytes(const GemmNTArgs& a, int variant) {
+  return a.M > 0 && gemm_nt_kfold_ok(a, variant) ? (size_t)a.M * 512 * sizeof(float) : 0;
 }
+size_t gemm_nt_workspace_bytes(const GemmNTArgs& a) { return gemm_nt_fold_bytes(a, a.variant >= 0 ? a.variant : g_flags.variant); }
 
 // grid + flush geometry of one launch of gemm_tn_w4_kernel over the group's tile list
 static void tn_w4_geometry(GemmTNGroup& G, int& n_runs, int& smax) {
@@ -2628,7 +2366,7 @@ static hipError_t tn_w4_launch(GemmTNGroup& G, hipStream_t st, void* ws, size_t 
 static bool tn_w4_ok(const GemmTNArgs& a, int M0) {
   const bool off32 = (double)a.M * a.ldp * 2 < 4.0e9 && (double)a.M * a.ldq * 2 < 4.0e9;
   return a.M == M0 && a.M > 0 && a.splits <= 0 && off32 && a.N1 % 256 == 0 && a.N2 % 256 == 0 && (a.q_group_n1 <= 0 || a.q_group_n1 % 256 == 0) &&
-         (a.use_tr < 0 ? g_tn_w4 != 0 : (a.use_tr & 8) == 0);
+         (a.use_tr < 0 ? g_flags.tn_w4 : (a.use_tr & 8) == 0);
 }
 size_t gemm_tn_group_workspace_bytes(const GemmTNArgs* list, int n) {
   // worst case over the ways launch_gemm_tn_group may run the list: one grouped launch, or one launch per problem (problems of different M)
@@ -2656,8 +2394,8 @@ size_t gemm_tn_group_workspace_bytes(const GemmTNArgs* list, int n) {
 hipError_t launch_gemm_tn(const GemmTNArgs& a, hipStream_t st) {
   if (a.M <= 0) return hipSuccess;
   if (a.N1 % 128 || a.N2 % 128) return hipErrorInvalidValue;
-  const bool use_tr = a.use_tr >= 0 ? (a.use_tr & 1) != 0 : g_use_tr;       // per-call override (opadpo_ctx_set_flags)
-  const bool tn_w4 = a.use_tr >= 0 ? (a.use_tr & 8) == 0 : g_tn_w4 != 0;
+  const bool use_tr = a.use_tr >= 0 ? (a.use_tr & 1) != 0 : g_flags.use_tr;      // per-call override (opadpo_ctx_set_flags)
+  const bool tn_w4 = a.use_tr >= 0 ? (a.use_tr & 8) == 0 : g_flags.tn_w4;
   const bool off32 = (double)a.M * a.ldp * 2 < 4.0e9 && (double)a.M * a.ldq * 2 < 4.0e9;
   if (tn_w4 && a.splits <= 0 && off32 && a.N1 % 256 == 0 && a.N2 % 256 == 0 && (a.q_group_n1 <= 0 || a.q_group_n1 % 256 == 0)) {
     GemmTNGroup G;
@@ -2907,104 +2645,351 @@ __global__ __launch_bounds__(64 * (NW + 2), NW == 8 ? 1 : 2) void gemm_nt_dec64x
 }
 }  // namespace
 
-int gemm_nt_dec64_splits(int N, int K, int splits);
-hipError_t launch_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, hipStream_t st) {
-  if (a.M <= 0) return hipSuccess;
-  if (a.M > 64 || a.N % 128 || a.K1 % D_BK || a.K1 <= 0 || a.K2 != 0 || a.lda1 % 8 || a.ldb1 % 8 || mode < 0 || mode > 2) return hipErrorInvalidValue;
-  if ((double)a.M * a.lda1 * 2 >= 4.0e9 || (double)a.N * a.ldb1 * 2 >= 4.0e9) return hipErrorInvalidValue;          // 32-bit buffer offsets
-  const int nt = a.K1 / D_BK, tiles = a.N / D_BN;
-  if (mode != 1) splits = 1;
-  splits = gemm_nt_dec64_splits(a.N, a.K1, splits);
-  const int mf = (a.M + 15) / 16;
-  // g_dec64_variant 1 keeps the LDS-ring kernel below (the kernel of rounds 2-4, the bit-for-bit reference of the tests); the register-streaming
-  // dec64r kernel of round 4 (q|k|v only, +3 %) is gone: dec64x beats it by 29 % there (profiles/r04_decode_stream.txt).
-  if (g_dec64_variant == 3 || g_dec64_variant == 0) {      // dec64x (the default): weights global -> registers in whole lines, activations through LDS in 256-deep chunks
-    // Rows per workgroup (16 x NW) by shape.  What bounds these launches is the vector-memory pipeline of a CU (weights + activation pieces,
-    // ~35 GB/s per CU whatever the source: profiles/r04_decode_stream.txt), so the estimate is bytes per CU = rounds of workgroups over the
-    // 256 CUs x (weight rows + token rows) of a workgroup: q|k|v (12288 rows) -> 48-row workgroups (256 of them), gate|up -> 128 rows
-    // (172), the K-split projections and the head -> 128 rows.
-    static const int nw_env = getenv("OPADPO_DEC64X_NW") ? atoi(getenv("OPADPO_DEC64X_NW")) : 0;      // diagnostics
-    const int nw_force = g_dec64x_nw == 1 ? 3 : g_dec64x_nw == 2 ? 4 : g_dec64x_nw == 3 ? 8 : nw_env;
-    int nw = 4;
-    {
-      long best = -1;
-      const int cand[4] = {8, 6, 4, 3};
-      for (int ci = 0; ci < 4; ++ci) {
-        const int c = cand[ci];
-        // 96-row workgroups (48 gate + 48 up rows) exist for the SwiGLU-pair mode only, where the last workgroup may be partly filled
-        if (mode == 2 ? (c == 3 || (c != 6 && a.N % (16 * c))) : (c == 6 || a.N % (16 * c))) continue;
-        const long wgs = (mode == 2 ? (long)(a.N / 2 + 8 * c - 1) / (8 * c) : (long)(a.N / (16 * c))) * splits;
-        long cost = ((wgs + 255) / 256) * (16 * c + 16 * mf);
-        if (c == 4 && wgs > 448 && wgs <= 512) cost = cost * 3 / 4;      // two full rounds of 64-row workgroups, two per CU: measured ahead of one round of 128-row ones (lm_head, 500: 46.8 vs 52.9 us at 8 tokens, 49.8 vs 53.6 at 32, 57.5 vs 57.9 at 64)
-        if (best < 0 || cost < best) { best = cost; nw = c; }
-      }
-      if (nw_force == 3 || nw_force == 4 || nw_force == 8) { if (a.N % (16 * nw_force) == 0 && !(mode == 2 && nw_force == 3)) nw = nw_force; }
-      if (nw_force == 6 && mode == 2) nw = 6;
-    }
-    const int grid_x = mode == 2 ? (a.N / 2 + 8 * nw - 1) / (8 * nw) : a.N / (16 * nw);
-#define DX_GO(MF_, MD_, NW_)                                                                                                          \
-  do {                                                                                                                                \
-    static bool at_ = false;                                                                                                          \
-    if (!at_) { (void)hipFuncSetAttribute((const void*)gemm_nt_dec64x_kernel<MF_, MD_, NW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * X_STAGE); at_ = true; } \
-    hipLaunchKernelGGL((gemm_nt_dec64x_kernel<MF_, MD_, NW_>), dim3(grid_x, splits), dim3(64 * (NW_ + 2)), 2 * X_STAGE, st, a); \
-  } while (0)
-#define DX_MF(MD_, NW_) do { if (mf == 1) DX_GO(1, MD_, NW_); else if (mf == 2) DX_GO(2, MD_, NW_); else if (mf == 3) DX_GO(3, MD_, NW_); else DX_GO(4, MD_, NW_); } while (0)
-#define DX_MODE(MD_) do { if (nw == 8) DX_MF(MD_, 8); else if (nw == 3) DX_MF(MD_, 3); else DX_MF(MD_, 4); } while (0)
-    if (mode == 0) DX_MODE(0);
-    else if (mode == 1) DX_MODE(1);
-    else { if (nw == 8) DX_MF(2, 8); else if (nw == 6) DX_MF(2, 6); else DX_MF(2, 4); }
-#undef DX_MODE
-#undef DX_MF
-#undef DX_GO
-    return hipGetLastError();
+// ==== gemm_nt dispatch: a pure plan of at most three launches from (arguments, flags, CU count), then one loop that launches it ========
+namespace {
+enum GemmSig { SIG_NT, SIG_NT_TILES, SIG_FOLD_REDUCE };      // kernel parameters: (GemmNTArgs), (GemmNTArgs, int n_tiles), gemm_fold2_reduce_kernel's
+struct GemmKernel { const char* name; const void* fn; int block, lds, sig; };
+#define GK(BLOCK, LDS, SIG, ...) {#__VA_ARGS__, (const void*)__VA_ARGS__, BLOCK, LDS, SIG}
+#define GK_W4(...) GK(256, 2 * P_STAGE, SIG_NT, gemm_nt_w4_kernel<__VA_ARGS__>)
+#define GK_W4S(...) GK(256, 2 * P_STAGE, SIG_NT_TILES, gemm_nt_w4s_kernel<__VA_ARGS__>)
+#define GK_SK(...) GK(512, 0, SIG_NT, gemm_nt_skinny_kernel<__VA_ARGS__>)
+#define GK_SK8(...) GK(512, 0, SIG_NT, gemm_nt_skinny8_kernel<__VA_ARGS__>)
+#define GK_DX(MD, NW) GK(64 * (NW + 2), 2 * X_STAGE, SIG_NT, gemm_nt_dec64x_kernel<1, MD, NW>), GK(64 * (NW + 2), 2 * X_STAGE, SIG_NT, gemm_nt_dec64x_kernel<2, MD, NW>), \
+                      GK(64 * (NW + 2), 2 * X_STAGE, SIG_NT, gemm_nt_dec64x_kernel<3, MD, NW>), GK(64 * (NW + 2), 2 * X_STAGE, SIG_NT, gemm_nt_dec64x_kernel<4, MD, NW>)
+#define GK_D64(MD, NS, KW) GK(256, NS * D_STAGE, SIG_NT, gemm_nt_dec64_kernel<1, MD, NS, KW>), GK(256, NS * D_STAGE, SIG_NT, gemm_nt_dec64_kernel<2, MD, NS, KW>), \
+                           GK(256, NS * D_STAGE, SIG_NT, gemm_nt_dec64_kernel<3, MD, NS, KW>), GK(256, NS * D_STAGE, SIG_NT, gemm_nt_dec64_kernel<4, MD, NS, KW>)
+// positions in the kernel table (below, same order); MF = 16-row fragments of the token rows ((M + 15) / 16), MF8 = 8-row ones
+enum : int {
+  K_X128, K_P8, K_TAIL8, K_TAIL4, K_FOLD_REDUCE,
+  K_W4,                  // + 2 * form + B first; form 0 default K-loop text, 1 bias / activation (BA), 2 DEEP text
+  K_W4S = K_W4 + 6,      // + 2 * form + B first; form 0 plain / fp32 residual / SwiGLU backward, 1 SwiGLU pair, 2 table-free rope, 3 DEEP text
+  K_SK = K_W4S + 8,      // + 4 * form + MF - 1; form 0 SwiGLU pair, 1 32 weight rows per workgroup, 2 16 rows
+  K_SK8 = K_SK + 12,     // + 4 * form + MF8 - 1; form 0 SwiGLU pair, 1 16 weight rows per workgroup, 2 32 rows (MF8 1 / 2)
+  K_DX = K_SK8 + 10,     // + 12 * mode + 4 * slot + MF - 1; slots: 3 / 4 / 8 weight waves (modes 0, 1), 4 / 6 / 8 (mode 2)
+  K_D64 = K_DX + 36,     // + MF - 1: 32-row workgroups (mode 0); + 4 + 8 * mode + 4 * deep ring + MF - 1
+  K_COUNT = K_D64 + 28
+};
+const GemmKernel g_kernels[] = {
+  GK(256, 65536, SIG_NT, gemm_nt_kernel_x<64, true, 2>), GK(512, 2 * P_STAGE, SIG_NT, gemm_nt_p8_kernel),
+  GK(256, 8 * 16384, SIG_NT, gemm_nt_tail64_kernel<8>), GK(256, 4 * 16384, SIG_NT, gemm_nt_tail64_kernel<4>),
+  GK(256, 0, SIG_FOLD_REDUCE, gemm_fold2_reduce_kernel),
+  GK_W4(false, false, false), GK_W4(true, false, false), GK_W4(false, true, false), GK_W4(true, true, false), GK_W4(false, false, true), GK_W4(true, false, true),
+  GK_W4S(false, 0, false), GK_W4S(true, 0, false), GK_W4S(false, 2, false), GK_W4S(true, 2, false),
+  GK_W4S(false, 3, false), GK_W4S(true, 3, false), GK_W4S(false, 0, true), GK_W4S(true, 0, true),
+  GK_SK(1, 2, 8, true), GK_SK(2, 2, 4, true), GK_SK(3, 2, 2, true), GK_SK(4, 2, 2, true),
+  GK_SK(1, 2, 8, false), GK_SK(2, 2, 4, false), GK_SK(3, 2, 2, false), GK_SK(4, 2, 2, false),
+  GK_SK(1, 1, 8, false), GK_SK(2, 1, 4, false), GK_SK(3, 1, 4, false), GK_SK(4, 1, 4, false),
+  GK_SK8(1, 2, 8, true), GK_SK8(2, 2, 4, true), GK_SK8(3, 2, 2, true), GK_SK8(4, 2, 2, true),
+  GK_SK8(1, 2, 8, false), GK_SK8(2, 2, 4, false), GK_SK8(3, 2, 2, false), GK_SK8(4, 2, 2, false),
+  GK_SK8(1, 4, 4, false), GK_SK8(2, 4, 2, false),
+  GK_DX(0, 3), GK_DX(0, 4), GK_DX(0, 8), GK_DX(1, 3), GK_DX(1, 4), GK_DX(1, 8), GK_DX(2, 4), GK_DX(2, 6), GK_DX(2, 8),
+  GK_D64(0, 4, 2), GK_D64(0, 4, 1), GK_D64(0, 8, 1), GK_D64(1, 4, 1), GK_D64(1, 8, 1), GK_D64(2, 4, 1), GK_D64(2, 8, 1),
+};
+#undef GK_D64
+#undef GK_DX
+#undef GK_SK8
+#undef GK_SK
+#undef GK_W4S
+#undef GK_W4
+#undef GK
+static_assert(sizeof(g_kernels) / sizeof(g_kernels[0]) == K_COUNT, "kernel table and its positions disagree");
+bool g_kernel_attr[K_COUNT];      // the dynamic-LDS attribute was set (the first launch of each kernel)
+
+struct GemmLaunch {
+  int kernel; dim3 grid; GemmNTArgs args;
+  int n_tiles;                    // SIG_NT_TILES: output tiles the streaming workgroups walk
+  const float* fold_ws;           // SIG_FOLD_REDUCE: the partial products (args: C, ldc, M, N, alpha of the caller's problem)
+};
+struct GemmPlan {
+  int n = 0;
+  GemmLaunch l[3];
+  size_t ws_bytes = 0;            // workspace the launches use (K-fold partial products)
+  void add(int kernel, dim3 grid, const GemmNTArgs& a, int n_tiles = 0, const float* fold_ws = nullptr) { l[n++] = {kernel, grid, a, n_tiles, fold_ws}; }
+};
+
+// the 4-wave 256x256 kernel over `tiles` output tiles.  Streaming form (gemm_nt_w4s_kernel, round 5) for the plain products whenever every workgroup gets at
+// least two tiles: one workgroup per CU walks the tile list and keeps its K-tile pipeline full across output tiles; variant 31: one tile per workgroup (cross-check).
+void plan_w4(GemmPlan& p, const GemmNTArgs& a, int tiles, const GemmFlags& f, int variant, int cus) {
+  const int ob = w4_b_first(a), nt = (a.K1 + a.K2) / P_BK, wgs = f.w4s_few ? 8 : cus;
+  const bool walk = variant != 31 && a.K1 / P_BK >= 3 && tiles >= 2 * wgs;
+  const bool plain = !a.bias && !a.rope_cos && !a.rope_pos && a.b1_fold_n == 0 && a.act == 0 && (!a.R || w4_direct_resid_ok(a));
+  int form = -1;
+  if (walk && nt <= 128) {
+    if (w4_direct_rope_pos_ok(a)) form = 2;
+    else if (plain || (!a.bias && !a.rope_cos && !a.rope_pos && a.b1_fold_n == 0 && (w4_direct_swiglu_bwd_ok(a) || w4_direct_swiglu_pair_ok(a)) && !a.swiglu_bwd_staged))
+      form = a.act == OPADPO_ACT_SWIGLU_PAIR ? 1 : 0;
+  } else if (walk && plain && !f.w4_nodeep) {
+    form = 3;      // > 128 K-tiles: streaming pays with the DEEP text only (default text: -4.7 %)
   }
-  static const int kw2_max = getenv("OPADPO_DEC64_KW2") ? atoi(getenv("OPADPO_DEC64_KW2")) : 256;      // diagnostics
-  if (mode == 0 && tiles <= kw2_max) {      // 32-row workgroups: twice the blocks for a projection that does not fill the chip
-    static bool at[5] = {false, false, false, false, false};
-    const dim3 g2(2 * tiles), b2(256);
-#define D_GO2(MF_)                                                                                                                    \
-  do {                                                                                                                                \
-    if (!at[MF_]) { (void)hipFuncSetAttribute((const void*)gemm_nt_dec64_kernel<MF_, 0, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * D_STAGE); at[MF_] = true; } \
-    hipLaunchKernelGGL((gemm_nt_dec64_kernel<MF_, 0, 4, 2>), g2, b2, 4 * D_STAGE, st, a);                                             \
-  } while (0)
-    if (mf == 1) D_GO2(1); else if (mf == 2) D_GO2(2); else if (mf == 3) D_GO2(3); else D_GO2(4);
-#undef D_GO2
-    return hipGetLastError();
-  }
-  const dim3 gr(tiles, splits), bl(256);
-  static const int deep_max = getenv("OPADPO_DEC64_DEEP") ? atoi(getenv("OPADPO_DEC64_DEEP")) : 256;      // diagnostics
-  const bool deep = tiles * splits <= deep_max;       // at most one workgroup per CU: a deeper ring instead of a second workgroup
-#define D_GO(MF_, MD_)                                                                                                             \
-  do {                                                                                                                             \
-    if (deep) {                                                                                                                    \
-      static bool at8 = false;                                                                                                     \
-      if (!at8) { (void)hipFuncSetAttribute((const void*)gemm_nt_dec64_kernel<MF_, MD_, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * D_STAGE); at8 = true; } \
-      hipLaunchKernelGGL((gemm_nt_dec64_kernel<MF_, MD_, 8>), gr, bl, 8 * D_STAGE, st, a);                                         \
-    } else {                                                                                                                       \
-      static bool at4 = false;                                                                                                     \
-      if (!at4) { (void)hipFuncSetAttribute((const void*)gemm_nt_dec64_kernel<MF_, MD_, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * D_STAGE); at4 = true; } \
-      hipLaunchKernelGGL((gemm_nt_dec64_kernel<MF_, MD_, 4>), gr, bl, 4 * D_STAGE, st, a);                                         \
-    }                                                                                                                              \
-  } while (0)
-#define D_MODE(MD_) do { if (mf == 1) D_GO(1, MD_); else if (mf == 2) D_GO(2, MD_); else if (mf == 3) D_GO(3, MD_); else D_GO(4, MD_); } while (0)
-  if (mode == 0) D_MODE(0); else if (mode == 1) D_MODE(1); else D_MODE(2);
-#undef D_MODE
-#undef D_GO
-  return hipGetLastError();
+  if (form >= 0) p.add(K_W4S + 2 * form + ob, dim3(wgs), a, tiles);
+  else p.add(K_W4 + (!f.w4_nodeep && nt >= 128 ? 4 : 0) + ob, dim3(tiles), a);      // the deep-K products (down, the dgrads): the DEEP text
 }
-int gemm_nt_dec64_splits(int N, int K, int splits) {
+
+hipError_t plan_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, const GemmFlags& f, GemmPlan& p);
+
+hipError_t plan_gemm_nt(const GemmNTArgs& a_in, const GemmFlags& f, int cus, void* ws, GemmPlan& p) {
+  if (a_in.M <= 0) return hipSuccess;
+  const int variant = a_in.variant >= 0 ? a_in.variant : f.variant;      // per-call override (opadpo_ctx_set_flags)
+  if (gemm_nt_kfold_ok(a_in, variant)) {      // the folded launch of the 256x256 kernel, then the pass that adds the halves
+    GemmNTArgs fo = a_in;
+    fo.N = 512; fo.K1 = a_in.K1 / 2; fo.a1_group_n = 256; fo.a1_group_stride = a_in.K1 / 2; fo.b1_fold_n = 256; fo.b1_fold_koff = a_in.K1 / 2;
+    fo.C = ws; fo.ldc = 512; fo.out_f32 = 1; fo.alpha = 1.0f;
+    const hipError_t e = plan_gemm_nt(fo, f, cus, ws, p);
+    if (e != hipSuccess) return e;
+    p.ws_bytes = gemm_nt_fold_bytes(a_in, variant);
+    p.add(K_FOLD_REDUCE, dim3((unsigned)(((size_t)a_in.M * (256 / 8) + 255) / 256)), a_in, 0, (const float*)ws);
+    return hipSuccess;
+  }
+  GemmNTArgs a = a_in;
+  // C leaves the 4-wave 256x256 kernel's direct epilogue as NON-TEMPORAL stores (round 4): at the end of a round all 256 workgroups write
+  // their 128-256 KiB of results at once - a 32-64 MB burst that drains at the fabric's write rate (the no-store diagnostic of the
+  // persistent-loop experiment put it at 4-5 us of a ~100 us tile) while nothing computes; streaming stores do not fight the operand
+  // panels for the 4-MiB L2s.  Same-box sustained A/B at M = 24576 (tools/ab_env.sh, profiles/r04_ab_nt_stores.txt): q|k|v +0.9 %, o
+  // (fp32 out) +2.5 %, gate|up +0.6 %, down (fp32 out) +1.0 %, N = 768 +1.2 %.
+  a.store_nt = 1;
+  // grouped tile order of the 256x256 4-wave kernel: 8 row tiles per group; 4 when the problem is at most 16 column tiles wide
+  // (N <= 4096: o / down and three of the four dgrads) - measured at M = 32362: down 1.363 -> 1.397 PF/s, o 1.394 -> 1.401,
+  // the wide projections lose 0.4-2 % with 4 or 6 and 6 % with 12.
+  a.group_m = a.N / P_BN <= 16 ? 4 : 8;
+  // 32-tile blocks dealt to the XCDs block-cyclically (round 6; common.h xcd_remap_cyclic): the eight XCDs of a round share one row group's A panels through the
+  // Infinity Cache and B stays within its reach between passes - down +2.0-5.3 %, gate|up +2.2-2.5 %, dgrad_gu +0.6-2.5 %, q|k|v +0.8-1.3 %, o +-0.2 %, step -1.0 %
+  // (profiles/r06z_ab_cyclic.txt).  opadpo_set_flags use_tr bit 12: the contiguous-chunk deal of rounds 1-5 (same results, bit for bit).
+  a.xcd_cyclic = !f.w4_chunk_deal;
+  const bool stream_hint = (a.act & OPADPO_GEMM_STREAM) != 0;
+  a.act &= 0xff;
+  if (a.N % BN || a.K1 % BK || a.K2 % BK || a.K1 + a.K2 <= 0) return hipErrorInvalidValue;
+  const int w4_tiles = ((a.M + P_BM - 1) / P_BM) * (a.N / P_BN);
+  if (a.b1_fold_n > 0) {      // K-folded problem (built above): every tile on gemm_nt_w4_kernel, the only kernel that reads the folded B1
+    if (a.N % P_BN || a.K1 % P_BK || a.K2) return hipErrorInvalidValue;
+    plan_w4(p, a, w4_tiles, f, variant, cus);
+    return hipSuccess;
+  }
+  // Decode-sized weight streams with nothing fused (no LoRA tail, bias, residual or scale; plain or SwiGLU-pair epilogue) go to the whole-line
+  // streaming kernel behind opadpo_gemm_nt_decode from 8 token rows up: the rollout's q|k|v, gate|up and lm_head at 8 sequences (decode step
+  // 3.79 -> 3.71 ms) and the lm_head at 9-64 (B=16: 4.42 -> 4.30 ms).  Below 8 rows the 8-row kernels are ahead in the step (B=5: 3.73 vs 3.86 ms,
+  // B=4: 3.41 vs 3.52; profiles/r04_decode_stream.txt section 16), and the projections with a residual epilogue (o, down) stay on them too.
+  if (a.M >= 8 && stream_hint && variant == 10 && f.dec64_variant != 1 && a.M <= 64 && a.K2 == 0 && !a.bias && !a.R && a.alpha == 1.0f &&
+      a.a1_group_n <= 0 && !a.rope_cos && !a.rope_pos && a.K1 % 64 == 0 && a.N % 128 == 0 && a.lda1 % 8 == 0 && a.ldb1 % 8 == 0 && a.ldc % 4 == 0 &&
+      (a.act == 0 || (a.act == OPADPO_ACT_SWIGLU_PAIR && !a.out_f32)) && (double)a.M * a.lda1 * 2 < 4.0e9 && (double)a.N * a.ldb1 * 2 < 4.0e9) {
+    GemmNTArgs d = a;
+    const int mode = a.act == OPADPO_ACT_SWIGLU_PAIR ? 2 : a.out_f32 ? 1 : 0;
+    d.act = 0;
+    return plan_gemm_nt_dec64(d, mode, 1, f, p);
+  }
+  if (a.rope_cos || a.rope_pos) {      // fused rotary embedding: only the 4-wave 256x256 kernel implements it (bf16 out, alpha-only epilogue)
+    const bool ok32 = (double)a.M * a.lda1 * 2 < 4.0e9 && (double)a.N * a.ldb1 * 2 < 4.0e9 &&
+                      (a.K2 == 0 || ((double)a.M * a.lda2 * 2 < 4.0e9 && (double)a.N * a.ldb2 * 2 < 4.0e9));
+    if (a.bias || a.act || a.R || a.out_f32 || a.N % P_BN || !ok32 || a.rope_cols % 128) return hipErrorInvalidValue;
+    if (a.rope_cos && (a.rope_L < 4 || (a.rope_seg_len > 0 && a.rope_seg_len < 4))) return hipErrorInvalidValue;
+    if (a.rope_pos && !(a.rope_l2theta > 0.f)) return hipErrorInvalidValue;
+    plan_w4(p, a, w4_tiles, f, variant, cus);
+    return hipSuccess;
+  }
+  if (a.act == OPADPO_ACT_SWIGLU_BWD) {       // fused SwiGLU backward epilogue (R = stored [gate | up], C = [d_gate | d_up]): the 4-wave 256x256 kernel only
+    const bool ok32 = (double)a.M * a.lda1 * 2 < 4.0e9 && (double)a.N * a.ldb1 * 2 < 4.0e9 &&
+                      (a.K2 == 0 || ((double)a.M * a.lda2 * 2 < 4.0e9 && (double)a.N * a.ldb2 * 2 < 4.0e9));
+    if (a.bias || !a.R || a.r_f32 || a.out_f32 || a.alpha != 1.0f || a.N % P_BN || !ok32 || a.ldr % 8 || a.ldc % 8 || a.rope_cos) return hipErrorInvalidValue;
+    plan_w4(p, a, w4_tiles, f, variant, cus);
+    return hipSuccess;
+  }
+  const bool decode = a.M <= 64 && ((stream_hint && variant == 10) || variant == 15);
+  if (a.act == OPADPO_ACT_SWIGLU_PAIR) {      // fused SwiGLU epilogue: the 4-wave 256x256 kernel, or the weight-streaming kernel for decode
+    const bool ok32 = (double)a.M * a.lda1 * 2 < 4.0e9 && (double)a.N * a.ldb1 * 2 < 4.0e9;
+    if (a.bias || a.R || a.out_f32 || a.alpha != 1.0f || a.K2 != 0 || a.N % P_BN || !ok32) return hipErrorInvalidValue;
+    if (decode && a.a1_group_n <= 0 && a.K1 % 32 == 0) {
+      if (f.skinny8 && (a.M <= 16 || (a.M <= 32 && a.N / 32 < 512))) p.add(K_SK8 + (a.M + 7) / 8 - 1, dim3(a.N / 16), a);      // same kernel family as the plain projection of this size
+      else p.add(K_SK + (a.M + 15) / 16 - 1, dim3(a.N / 32), a);
+      return hipSuccess;
+    }
+    plan_w4(p, a, w4_tiles, f, variant, cus);
+    return hipSuccess;
+  }
+  // decode-sized problems (M <= 64): weight-streaming kernel, one workgroup per 16 (or 32) weight rows
+  if (decode) {
+    const int mf = (a.M + 15) / 16;
+    // 32 weight rows per workgroup halve the activation re-reads from L2 (they bound the kernel from M ~ 32 on) but also the
+    // number of blocks: measured better only while >= 384 blocks remain (N = 4096 at 128 blocks: 29 vs 24 us at M = 64)
+    const bool wide = a.N % 32 == 0 && a.N / 32 >= (mf >= 3 ? 384 : 512) && (a.a1_group_n <= 0 || a.a1_group_n % 32 == 0) &&
+                      (a.a2_group_n <= 0 || a.a2_group_n % 32 == 0);
+    if (f.skinny8 && a.M > 16 && a.M <= 32 && !wide && (a.a1_group_n <= 0 || a.a1_group_n % 16 == 0) && (a.a2_group_n <= 0 || a.a2_group_n % 16 == 0)) {
+      // 17..32 tokens, narrow N (q|k|v, o, down at 7B): the whole-cache-line form still wins (M = 24: 37 -> 31, 15 -> 13, 37 -> 28 us);
+      // the 32-row form above keeps the wide projections (activation re-reads from L2 dominate there)
+      p.add(K_SK8 + 4 + (a.M + 7) / 8 - 1, dim3(a.N / 16), a);
+    } else if (f.skinny8 && a.M <= 16 && (a.a1_group_n <= 0 || a.a1_group_n % 32 == 0) && (a.a2_group_n <= 0 || a.a2_group_n % 32 == 0)) {
+      const bool wide8 = a.N % 32 == 0 && a.N / 32 >= 512;          // 32 weight rows per workgroup while >= 2 rounds of blocks remain
+      p.add(K_SK8 + (wide8 ? 8 : 4) + (a.M + 7) / 8 - 1, dim3(wide8 ? a.N / 32 : a.N / 16), a);
+    } else {
+      p.add(K_SK + (wide ? 4 : 8) + mf - 1, dim3(wide ? a.N / 32 : a.N / 16), a);
+    }
+    return hipSuccess;
+  }
+  // variant 10 (default, "auto"): a 256x256 kernel when it yields at least ~1.25 rounds of blocks on the 256 CUs (or fills its
+  // last round), the 128x128 kernel otherwise (skinny LoRA GEMMs, N not a multiple of 256).
+  const bool off32 = (double)a.M * a.lda1 * 2 < 4.0e9 && (double)a.N * a.ldb1 * 2 < 4.0e9 &&
+                     (a.K2 == 0 || ((double)a.M * a.lda2 * 2 < 4.0e9 && (double)a.N * a.ldb2 * 2 < 4.0e9));   // buffer offsets are 32-bit
+  const int pp_tiles = (a.N % P_BN == 0 && off32) ? w4_tiles : 0;
+  // one 256x256 block per CU and round: below 1.25 rounds the big tile only pays when its last round fills the chip
+  // (M = 32362: N = 512 -> 254 blocks, w4 1.10-1.18 PF/s vs 0.75-0.79 for the 128x128 kernel; N = 768 -> 381 blocks = 1.49
+  // rounds, w4 1.10 vs 0.84; N = 256 -> 127 blocks, the 128x128 kernel wins 0.77 vs 0.63)
+  // the 4-wave kernels' hot instantiations take alpha-only epilogues; bias / quick-GELU / GELU problems (+ an fp32 residual into an fp32 result) run on
+  // their BA instantiations (round 5: the vision tower's and the projector's GEMMs left the 8-wave kernel / the 128x128 kernel for them)
+  const bool ba = (variant == 10 || variant == 31) && w4_direct_ba_ok(a) && a.N % P_BN == 0 && off32 &&
+                  (double)(a.M + 256) * a.ldc * (a.out_f32 ? 4 : 2) < 4.0e9;
+  const bool plain = (!a.bias && !a.act) || ba;
+  const int pp_slots = ((pp_tiles + 255) / 256) * 256;
+  // ragged rows (M ~ 24-26 k): N = 512 -> 188-200 blocks in ONE round, w4 0.088 / 0.256 ms (K = 4096 / 11008) vs 0.121 / 0.424 for the
+  // 128x128 kernel; N = 768 -> 282-300 blocks: a tie; N = 256 -> 94-100 blocks: the 128x128 kernel keeps a 5-20 % lead
+  // with the quarter-tile tail (below) a second, short round costs 0.5-0.6 of a round: N = 768 (282-300 blocks) moves to the 256x256 kernel as
+  // well, and a deep-K one-round problem of <= 128 tiles (x . A_d^T: N = 256, K = 11008) runs as quarter tiles entirely (4x the blocks)
+  const int pp_rem = pp_tiles % 256, pp_nt = (a.K1 + a.K2) / P_BK;
+  const bool deep_small = plain && pp_tiles >= 64 && pp_tiles <= 128 && pp_nt >= 128;      // K = 4096 one-round problems measured no gain (0.085 vs 0.081 ms)
+  const bool big = variant == 17 || variant == 31 || (f.w4s_few && variant == 10 && plain && pp_tiles >= 16) ||      // (test switch: small problems stream on 8 workgroups)
+                   (variant != 4 && (pp_tiles >= 320 || (plain && pp_tiles >= 150 && (pp_tiles <= 256 || pp_rem <= 128)) || deep_small ||
+                                     (plain && pp_tiles >= 200 && pp_tiles * 100 >= pp_slots * 88)));
+  if (big && pp_tiles > 0) {
+    if (!plain || variant == 17) {        // bias / activation epilogues (vision tower, projector): 8 waves x 128x64, 4 phases per K-tile
+      p.add(K_P8, dim3(pp_tiles), a);
+      return hipSuccess;
+    }
+    // 4 waves x 128x128, long-lead DMA schedule, M0 one MFMA ahead of each DMA
+    const int full = pp_tiles / 256 * 256, rem = pp_tiles - full;
+    // a partly filled last round (<= 64 tiles) runs as QUARTER tiles on the 128x128 kernel - 4 blocks per 256x256 tile, each over the
+    // FULL K range in the same k order, so every element of C is bit-identical to what the 256x256 kernel writes and the result of a row
+    // does not depend on how many rows share the batch (WHICH tiles are tail tiles depends on M).
+    // (a deep-K problem of <= 128 tiles - x . A_d^T: N = 256, K = 11008 - runs as quarter tiles entirely: 4x the blocks on a chip it
+    // would fill to a third; variant 31 = the 256x256 kernel on every tile, the bit-for-bit cross-check of the tests).
+    // Measured (GB_ONLY=tail, N = 4096): a 16- or 64-tile tail costs 0.5-0.6 of a round as quarter tiles, a 128-tile tail 1.1-1.3 rounds
+    // (two quarter blocks share a CU there) - more than the plain partly filled round: quarter tiles up to 64 tiles only.
+    // Round 2's split-K tail (2 / 4 / 8 K-slices per tail tile + a reduce launch, a process-global fp32 workspace) was 1.1 % faster per step
+    // (964.4 vs 975.2 ms; no tail handling: 982.8) but re-associated the fp32 sums of the tail tiles, i.e. made a row's result depend on
+    // the batch's row count; removed.
+    const bool tail = variant != 31 && (full > 0 || deep_small) && rem > 0 && rem <= (deep_small && full == 0 ? 128 : 64);
+    const int body = tail ? full : pp_tiles;
+    if (body > 0) {
+      if (ba) p.add(K_W4 + 2 + (a.N / P_BN <= 16), dim3(body), a);      // BA instantiations: one tile per workgroup only - the streaming kernel has no registers
+      else plan_w4(p, a, body, f, variant, cus);                       // left for the bias / activation epilogue (it spills, and an asm K-loop must not touch scratch)
+    }
+    if (!tail) return hipSuccess;
+    GemmNTArgs t = a;
+    t.quarter = 1; t.tile0 = full;
+    // (a four-stage ring for these blocks - three K-tiles in flight, one block per CU - measured 973.1 vs 969.9 ms per step: no gain,
+    // a lone 4-wave 128x128 block runs at ~0.6 PF/s per CU whatever its prefetch depth; removed)
+    // (round 4) tails of a multi-round launch run as SIXTEENTH tiles (16 blocks of 64x64 per tile: a 16-tile tail already fills the chip);
+    // the deep-K one-round problem keeps its quarter tiles (every tile of it is a "tail" tile: rate matters there).
+    // Measured (GB_ONLY=tail, N = 4096; quarter tiles -> sixteenth tiles): 16-tile tail +38 -> +24 us (K = 4096), +115 -> +44 us (K = 11008);
+    // 32 tiles +51 -> +34, +115 -> +82; 48 tiles: a tie; 64 tiles (1024 blocks, four per CU): +50 -> +65, i.e. quarter tiles from 48 tiles on.
+    if (full > 0 && rem <= 40) p.add(rem <= 16 ? K_TAIL8 : K_TAIL4, dim3(rem * 16), t);
+    else p.add(K_X128, dim3(rem * 4), t);
+    return hipSuccess;
+  }
+  p.add(K_X128, dim3(((a.M + BM - 1) / BM) * (a.N / BN)), a);      // everything else (and variant 4): the 128x128 kernel
+  return hipSuccess;
+}
+
+int dec64_splits(int N, int K, int splits, const GemmFlags& f) {
   const int nt = K / D_BK, tiles = N / D_BN;
   if (splits <= 0) {
     // workgroup target of the K-split, counted in 64-row tiles: 256 = four K-slices for the 7B o / down projections (the dec64x kernel then
     // runs them as 64-row workgroups x 4 slices).  Half the slices of round 2's target of 512 are half the partial tiles for the RMSNorm that
     // adds them: decode step B = 64 8.00 -> 7.90 ms, B = 32 5.65 -> 5.59 (384: 8.03, 128: 8.42; profiles/r04_decode_stream.txt section 6).
-    // The LDS-ring kernel (OPADPO_DEC64_V=1) keeps 512.
-    static const int env_target = getenv("OPADPO_DEC64_BLOCKS") ? atoi(getenv("OPADPO_DEC64_BLOCKS")) : 0;      // diagnostics
-    const int target = env_target > 0 ? env_target : (g_dec64_variant == 1 ? 512 : 256);
+    // The LDS-ring kernel (use_tr bits 5-6 = 1) keeps 512.
+    const int target = f.dec64_variant == 1 ? 512 : 256;
     splits = (target + tiles - 1) / tiles;
     if (splits > nt / 4) splits = nt / 4 > 0 ? nt / 4 : 1;
   }
   return splits > nt ? nt : splits;
+}
+
+hipError_t plan_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, const GemmFlags& f, GemmPlan& p) {
+  if (a.M <= 0) return hipSuccess;
+  if (a.M > 64 || a.N % 128 || a.K1 % D_BK || a.K1 <= 0 || a.K2 != 0 || a.lda1 % 8 || a.ldb1 % 8 || mode < 0 || mode > 2) return hipErrorInvalidValue;
+  if ((double)a.M * a.lda1 * 2 >= 4.0e9 || (double)a.N * a.ldb1 * 2 >= 4.0e9) return hipErrorInvalidValue;          // 32-bit buffer offsets
+  const int tiles = a.N / D_BN, mf = (a.M + 15) / 16;
+  splits = dec64_splits(a.N, a.K1, mode != 1 ? 1 : splits, f);
+  // dec64_variant 1 / 2 keeps the LDS-ring kernel below (the kernel of rounds 2-4, the bit-for-bit reference of the tests); the register-streaming
+  // dec64r kernel of round 4 (q|k|v only, +3 %) is gone: dec64x beats it by 29 % there (profiles/r04_decode_stream.txt).
+  if (f.dec64_variant == 3 || f.dec64_variant == 0) {      // dec64x (the default): weights global -> registers in whole lines, activations through LDS in 256-deep chunks
+    // Rows per workgroup (16 x NW) by shape.  What bounds these launches is the vector-memory pipeline of a CU (weights + activation pieces,
+    // ~35 GB/s per CU whatever the source: profiles/r04_decode_stream.txt), so the estimate is bytes per CU = rounds of workgroups over the
+    // 256 CUs x (weight rows + token rows) of a workgroup: q|k|v (12288 rows) -> 48-row workgroups (256 of them), gate|up -> 128 rows
+    // (172), the K-split projections and the head -> 128 rows.
+    int nw = 4;
+    long best = -1;
+    for (const int c : {8, 6, 4, 3}) {
+      // 96-row workgroups (48 gate + 48 up rows) exist for the SwiGLU-pair mode only, where the last workgroup may be partly filled
+      if (mode == 2 ? (c == 3 || (c != 6 && a.N % (16 * c))) : (c == 6 || a.N % (16 * c))) continue;
+      const long wgs = (mode == 2 ? (long)(a.N / 2 + 8 * c - 1) / (8 * c) : (long)(a.N / (16 * c))) * splits;
+      long cost = ((wgs + 255) / 256) * (16 * c + 16 * mf);
+      if (c == 4 && wgs > 448 && wgs <= 512) cost = cost * 3 / 4;      // two full rounds of 64-row workgroups, two per CU: measured ahead of one round of 128-row ones (lm_head, 500: 46.8 vs 52.9 us at 8 tokens, 49.8 vs 53.6 at 32, 57.5 vs 57.9 at 64)
+      if (best < 0 || cost < best) { best = cost; nw = c; }
+    }
+    const int nw_force = f.dec64x_nw == 1 ? 3 : f.dec64x_nw == 2 ? 4 : f.dec64x_nw == 3 ? 8 : 0;
+    if (nw_force && a.N % (16 * nw_force) == 0 && !(mode == 2 && nw_force == 3)) nw = nw_force;
+    const int slot = nw == 8 ? 2 : nw == (mode == 2 ? 4 : 3) ? 0 : 1;      // modes 0, 1: 3 / 4 / 8 weight waves; mode 2: 4 / 6 / 8
+    p.add(K_DX + 12 * mode + 4 * slot + mf - 1, dim3(mode == 2 ? (a.N / 2 + 8 * nw - 1) / (8 * nw) : a.N / (16 * nw), splits), a);
+    return hipSuccess;
+  }
+  if (mode == 0 && tiles <= 256) p.add(K_D64 + mf - 1, dim3(2 * tiles), a);      // 32-row workgroups: twice the blocks for a projection that does not fill the chip
+  else p.add(K_D64 + 4 + 8 * mode + (tiles * splits <= 256 ? 4 : 0) + mf - 1, dim3(tiles, splits), a);      // at most one workgroup per CU: a deeper ring instead of a second workgroup
+  return hipSuccess;
+}
+
+hipError_t launch_plan(const GemmPlan& p, hipStream_t st) {
+  for (int i = 0; i < p.n; ++i) {
+    const GemmLaunch& l = p.l[i];
+    const GemmKernel& k = g_kernels[l.kernel];
+    if (!g_kernel_attr[l.kernel]) {
+      if (k.lds > 0) (void)hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
+      g_kernel_attr[l.kernel] = true;
+    }
+    GemmNTArgs args = l.args;
+    int n_tiles = l.n_tiles, ldc = args.ldc, M = args.M, N = args.N;
+    const float* ws = l.fold_ws;
+    bf16_t* C = (bf16_t*)args.C;
+    float alpha = args.alpha;
+    void* nt_args[] = {&args, &n_tiles};
+    void* reduce_args[] = {&ws, &C, &ldc, &M, &N, &alpha};
+    if (hipLaunchKernel(k.fn, l.grid, dim3(k.block), k.sig == SIG_FOLD_REDUCE ? reduce_args : nt_args, k.lds, st) != hipSuccess) break;
+  }
+  return hipGetLastError();
+}
+
+int device_cus() {
+  static const int cus = [] {
+    int dev = 0;
+    hipDeviceProp_t pr;
+    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256;
+  }();
+  return cus;
+}
+}  // namespace
+
+hipError_t launch_gemm_nt(const GemmNTArgs& a, hipStream_t st, void* ws, size_t ws_bytes) {
+  GemmPlan p;
+  const hipError_t e = plan_gemm_nt(a, g_flags, device_cus(), ws, p);
+  if (e != hipSuccess) return e;
+  if (p.ws_bytes > (ws ? ws_bytes : 0)) return hipErrorInvalidValue;      // the caller sizes the workspace with gemm_nt_workspace_bytes
+  return launch_plan(p, st);
+}
+hipError_t launch_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, hipStream_t st) {
+  GemmPlan p;
+  const hipError_t e = plan_gemm_nt_dec64(a, mode, splits, g_flags, p);
+  return e != hipSuccess ? e : launch_plan(p, st);
+}
+int gemm_nt_dec64_splits(int N, int K, int splits) { return dec64_splits(N, K, splits, g_flags); }
+hipError_t gemm_nt_plan_text(const GemmNTArgs& a, int gemm_variant, int use_tr, int cus, char* out, size_t out_len) {
+  GemmPlan p;
+  const hipError_t e = plan_gemm_nt(a, gemm_flags(gemm_variant, use_tr), cus, nullptr, p);
+  if (e != hipSuccess) return e;
+  size_t used = 0;
+  if (out_len) out[0] = 0;
+  for (int i = 0; i < p.n; ++i) {
+    const GemmKernel& k = g_kernels[p.l[i].kernel];
+    const int w = snprintf(out + used, out_len - used, "%s %u %u %d %d\n", k.name, p.l[i].grid.x, p.l[i].grid.y, k.block, k.lds);
+    if (w < 0 || (size_t)w >= out_len - used) return hipErrorInvalidValue;
+    used += w;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_gemm_tn_group(const GemmTNArgs* list, int n, hipStream_t st, void* workspace, size_t workspace_bytes, int* all_ordered) {

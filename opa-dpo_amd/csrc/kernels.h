@@ -104,7 +104,11 @@ int opadpo_report_done(hipError_t e, const char* where);
 bool opadpo_flag_tr();
 void opadpo_set_attn_dma(bool on);
 
-hipError_t launch_gemm_nt(const GemmNTArgs& a, hipStream_t st);
+// ws / ws_bytes: workspace of the K-folded products, at least gemm_nt_workspace_bytes(a) (0 for every other problem); used in stream order
+hipError_t launch_gemm_nt(const GemmNTArgs& a, hipStream_t st, void* ws, size_t ws_bytes);
+size_t gemm_nt_workspace_bytes(const GemmNTArgs& a);
+// the launches launch_gemm_nt would make under opadpo_set_flags(gemm_variant, use_tr) on `cus` CUs, one line each: kernel grid.x grid.y block LDS
+hipError_t gemm_nt_plan_text(const GemmNTArgs& a, int gemm_variant, int use_tr, int cus, char* out, size_t out_len);
 hipError_t launch_gemm_tn(const GemmTNArgs& a, hipStream_t st);
 // all problems must share M and be eligible for the 256x256 kernel (N1, N2 % 256 == 0, q_group_n1 % 256 == 0); otherwise the
 // problems are launched one by one

@@ -131,6 +131,301 @@ def test_decode_attention_key_range_rule(built_lib):
     assert f(0, nh, hd, ctx) == 0
 
 
+def test_gemm_nt_routing_rule(built_lib):
+    """Host-side kernel choice of opadpo_gemm_nt, read through opadpo_debug_gemm_nt_plan (a test entry point outside the header: the same
+    validation, then the launches the dispatch would make on `cus` CUs as `kernel grid.x grid.y block LDS` lines; nothing is launched).  Pins
+    kernel + grid of the product path's GEMMs at the 7B / 13B benchmark row counts and at ragged ones, the K-folded N = 256 LoRA products,
+    the vision tower's bias / activation GEMMs, the tail forms, the decode routes and every gemm_variant / use_tr bit the GPU tests use as a
+    cross-check (opadpo_set_flags)."""
+    lib = ctypes.CDLL(built_lib)
+    f = lib.opadpo_debug_gemm_nt_plan
+    f.restype = ctypes.c_int
+    _p, _i = ctypes.c_void_p, ctypes.c_int
+    f.argtypes = [_p, _i, _p, _i, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _i, ctypes.c_float, _i,
+                  _i, _i, _i, _i, ctypes.c_char_p, _i]
+    S = 0x100      # OPADPO_GEMM_STREAM
+
+    def plan(M, N, K1, K2=0, a2g=0, a2s=0, a1g=0, a1s=0, lda1=0, out_f32=0, R=0, ldr=0, bias=0, alpha=1.0, act=0, ldc=0, var=10, tr=1, rope=0,
+             cus=256):      # R: 1 an fp32 residual, 2 a bf16 operand
+        buf = ctypes.create_string_buffer(4096)
+        rc = f(0x1000, lda1 or K1, 0x2000, K1, K1, 0x3000 if K2 else None, K2, 0x4000 if K2 else None, K2, K2, a2g, a2s, a1g, a1s,
+               0x5000, ldc or N, out_f32, 0x6000 if R else None, ldr or N, int(R == 1), 0x7000 if bias else None, M, N, alpha, act, var, tr, rope, cus, buf, 4096)
+        assert rc == 0
+        out = []
+        for ln in buf.value.decode().splitlines():      # "gemm_nt_w4s_kernel<true, 0, false> 256 1 256 131072" -> "w4s<true, 0, false> 256"
+            name, gx, gy = ln[:ln.rindex(">") + 1] if ">" in ln else ln.split()[0], *ln.rsplit(" ", 4)[1:3]
+            out.append(name.replace("gemm_nt_", "").replace("_kernel", "") + f" {gx}" + (f"x{gy}" if gy != "1" else ""))
+        return out
+
+    def step(H, F, r, V, M):      # one decoder layer of the LoRA product path (forward, then the dgrads of the backward) and the head
+        return [dict(M=M, N=3 * r, K1=H, alpha=2.0),                                   # t_qkv = x A_qkv^T
+                dict(M=M, N=3 * H, K1=H, K2=3 * r, a2g=H, a2s=r, rope=2),              # q|k|v + LoRA tail, table-free rope
+                dict(M=M, N=r, K1=H, alpha=2.0),                                       # t_o (K-folded)
+                dict(M=M, N=H, K1=H, K2=r, out_f32=1, R=1),                            # o + tail into the fp32 residual stream
+                dict(M=M, N=2 * r, K1=H, alpha=2.0),                                   # t_gu
+                dict(M=M, N=2 * F, K1=H, K2=2 * r, a2g=F, a2s=r),                      # gate|up + tail
+                dict(M=M, N=2 * F, K1=H, act=3, ldc=F),                                # gate|up with the SwiGLU pair epilogue (merged reference)
+                dict(M=M, N=r, K1=F, alpha=2.0),                                       # t_d (K-folded)
+                dict(M=M, N=H, K1=F, K2=r, out_f32=1, R=1),                            # down + tail, fp32 residual
+                dict(M=M, N=r, K1=H, alpha=2.0),                                       # dt_d = dY B_d (K-folded)
+                dict(M=M, N=F, K1=H, K2=r, act=4, R=2, ldr=2 * F, ldc=2 * F),          # d_act . W_d with the SwiGLU backward epilogue (R: bf16 [gate | up])
+                dict(M=M, N=2 * r, K1=F, lda1=2 * F, a1g=r, a1s=F, alpha=2.0),         # dt_gu (grouped A)
+                dict(M=M, N=H, K1=2 * F, K2=2 * r),                                    # d_n = d_gu W_gu + tail
+                dict(M=M, N=r, K1=H, alpha=2.0),                                       # dt_o (K-folded)
+                dict(M=M, N=H, K1=H, K2=r),                                            # d_attn = d_h W_o + tail
+                dict(M=M, N=3 * r, K1=H, lda1=3 * H, a1g=r, a1s=H, alpha=2.0),         # dt_qkv (grouped A)
+                dict(M=M, N=H, K1=3 * H, K2=3 * r),                                    # d_n = dqkv W_qkv + tail
+                dict(M=M, N=V, K1=H, out_f32=1)]                                       # lm_head
+
+    assert [plan(**k) for k in step(4096, 11008, 256, 32000, 32362)] == [
+        ["w4<true, false, false> 381"],
+        ["w4s<true, 3, false> 256"],
+        ["w4<true, false, false> 254", "gemm_fold2_reduce 4046"],
+        ["w4s<true, 0, false> 256"],
+        ["w4<true, false, false> 254"],
+        ["w4s<false, 0, false> 256"],
+        ["w4s<false, 2, false> 256"],
+        ["w4<true, false, false> 254", "gemm_fold2_reduce 4046"],
+        ["w4s<true, 0, true> 256"],
+        ["w4<true, false, false> 254", "gemm_fold2_reduce 4046"],
+        ["w4s<true, 0, false> 256"],
+        ["w4<true, false, true> 254"],
+        ["w4s<true, 0, true> 256"],
+        ["w4<true, false, false> 254", "gemm_fold2_reduce 4046"],
+        ["w4s<true, 0, false> 256"],
+        ["w4<true, false, false> 381"],
+        ["w4s<true, 0, true> 256"],
+        ["w4s<false, 0, false> 256", "tail64<8> 48"]]
+    assert [plan(**k) for k in step(4096, 11008, 256, 32000, 24890)] == [
+        ["w4<true, false, false> 256", "tail64<4> 608"],
+        ["w4s<true, 3, false> 256"],
+        ["w4<true, false, false> 196", "gemm_fold2_reduce 3112"],
+        ["w4s<true, 0, false> 256", "tail64<4> 512"],
+        ["w4<true, false, false> 196"],
+        ["w4s<false, 0, false> 256"],
+        ["w4s<false, 2, false> 256"],
+        ["w4<true, false, false> 196", "gemm_fold2_reduce 3112"],
+        ["w4s<true, 0, true> 256", "tail64<4> 512"],
+        ["w4<true, false, false> 196", "gemm_fold2_reduce 3112"],
+        ["w4s<true, 0, false> 256"],
+        ["w4<true, false, true> 196"],
+        ["w4s<true, 0, true> 256", "tail64<4> 512"],
+        ["w4<true, false, false> 196", "gemm_fold2_reduce 3112"],
+        ["w4s<true, 0, false> 256", "tail64<4> 512"],
+        ["w4<true, false, false> 256", "tail64<4> 608"],
+        ["w4s<true, 0, true> 256", "tail64<4> 512"],
+        ["w4s<false, 0, false> 256"]]
+    assert [plan(**k) for k in step(5120, 13824, 256, 32000, 17652)] == [
+        ["w4<true, false, false> 207"],
+        ["w4s<true, 3, false> 256"],
+        ["w4<true, false, false> 138", "gemm_fold2_reduce 2207"],
+        ["w4s<true, 0, false> 256"],
+        ["kernel_x<64, true, 2> 552"],
+        ["w4s<false, 0, false> 256", "tail64<4> 448"],
+        ["w4s<false, 2, false> 256"],
+        ["w4<true, false, false> 138", "gemm_fold2_reduce 2207"],
+        ["w4s<false, 0, true> 256"],
+        ["w4<true, false, false> 138", "gemm_fold2_reduce 2207"],
+        ["w4s<true, 0, false> 256"],
+        ["kernel_x<64, true, 2> 552"],
+        ["w4s<false, 0, true> 256"],
+        ["w4<true, false, false> 138", "gemm_fold2_reduce 2207"],
+        ["w4s<true, 0, false> 256"],
+        ["w4<true, false, false> 207"],
+        ["w4s<false, 0, true> 256"],
+        ["w4s<false, 0, false> 256"]]
+    assert [plan(**k) for k in step(5120, 13824, 256, 32000, 13001)] == [
+        ["w4<true, false, false> 153"],
+        ["w4s<true, 3, false> 256"],
+        ["w4<true, false, false> 102", "gemm_fold2_reduce 1626"],
+        ["w4s<true, 0, false> 256"],
+        ["kernel_x<64, true, 2> 408"],
+        ["w4s<false, 0, false> 256"],
+        ["w4s<false, 2, false> 256"],
+        ["w4<true, false, false> 102", "gemm_fold2_reduce 1626"],
+        ["w4s<false, 0, true> 256"],
+        ["w4<true, false, false> 102", "gemm_fold2_reduce 1626"],
+        ["w4s<true, 0, false> 256"],
+        ["kernel_x<64, true, 2> 408"],
+        ["w4s<false, 0, true> 256"],
+        ["w4<true, false, false> 102", "gemm_fold2_reduce 1626"],
+        ["w4s<true, 0, false> 256"],
+        ["w4<true, false, false> 153"],
+        ["w4s<false, 0, true> 256"],
+        ["w4s<false, 0, false> 256"]]
+
+    # N = 256 products below K = 1024 are not folded; the folded launch keeps its shape whatever the flags of the 256x256 kernel
+    assert plan(M=32362, N=256, K1=768) == ["kernel_x<64, true, 2> 506"]
+    assert plan(M=24890, N=256, K1=512, alpha=2.0) == ["kernel_x<64, true, 2> 390"]
+    assert plan(M=32362, N=256, K1=4096, var=31) == ["w4<true, false, false> 254", "gemm_fold2_reduce 4046"]
+    assert plan(M=32362, N=256, K1=11008, tr=2049) == ["w4<true, false, false> 254", "gemm_fold2_reduce 4046"]
+    assert plan(M=32362, N=256, K1=11008, tr=1025) == ["w4<true, false, false> 254", "gemm_fold2_reduce 4046"]
+    assert plan(M=40, N=256, K1=4096) == ["w4<true, false, false> 2", "gemm_fold2_reduce 5"]
+    assert plan(M=32362, N=256, K1=4096, var=4) == ["kernel_x<64, true, 2> 506"]
+    assert plan(M=32362, N=256, K1=4096, act=S) == ["kernel_x<64, true, 2> 506"]
+    # vision tower (22 images x 577 positions) and projector (x 576): bias / activation epilogues
+    assert plan(M=12694, N=1024, K1=640, bias=1) == ["w4<true, true, false> 200"]
+    assert plan(M=12694, N=3072, K1=1024, bias=1) == ["w4<true, true, false> 600"]
+    assert plan(M=12694, N=1024, K1=1024, bias=1, out_f32=1, R=1) == ["w4<true, true, false> 200"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=12694, N=1024, K1=4096, bias=1, out_f32=1, R=1) == ["w4<true, true, false> 200"]
+    assert plan(M=12672, N=4096, K1=1024, bias=1, act=2) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=12672, N=4096, K1=4096, bias=1) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    # tails of a multi-round launch: <= 16 tiles sixteenth tiles with the deep ring, <= 40 sixteenth tiles, <= 64 quarter tiles; a deep-K
+    # one-round problem of 64-128 tiles as quarter tiles entirely (fp32 out: not folded)
+    assert plan(M=4097, N=4096, K1=4096) == ["w4<true, false, false> 256", "tail64<8> 256"]
+    assert plan(M=4097, N=4096, K1=11008, out_f32=1, R=1) == ["w4<true, false, true> 256", "tail64<8> 256"]
+    assert plan(M=2305, N=8192, K1=4096) == ["w4<true, false, false> 256", "kernel_x<64, true, 2> 256"]
+    assert plan(M=4097, N=12288, K1=4096) == ["w4s<true, 0, false> 256", "kernel_x<64, true, 2> 192"]
+    assert plan(M=24890, N=256, K1=11008, out_f32=1) == ["kernel_x<64, true, 2> 392"]
+    assert plan(M=4097, N=4096, K1=4096, var=31) == ["w4<true, false, false> 272"]
+    # decode (stream hint), 7B projections: q|k|v, o (fp32 residual), gate|up, SwiGLU pair, down (fp32 residual), lm_head
+    def decode(M):
+        return [plan(M=M, N=12288, K1=4096, act=S), plan(M=M, N=4096, K1=4096, out_f32=1, R=1, act=S), plan(M=M, N=22016, K1=4096, act=S),
+                plan(M=M, N=22016, K1=4096, act=S | 3, ldc=11008), plan(M=M, N=4096, K1=11008, out_f32=1, R=1, act=S),
+                plan(M=M, N=32000, K1=4096, out_f32=1, act=S)]
+
+    assert decode(1) == [["skinny8<1, 2, 8, false> 768"], ["skinny8<1, 2, 8, false> 256"], ["skinny8<1, 4, 4, false> 688"], ["skinny8<1, 2, 8, true> 1376"], ["skinny8<1, 2, 8, false> 256"], ["skinny8<1, 4, 4, false> 1000"]]
+    assert decode(4) == [["skinny8<1, 2, 8, false> 768"], ["skinny8<1, 2, 8, false> 256"], ["skinny8<1, 4, 4, false> 688"], ["skinny8<1, 2, 8, true> 1376"], ["skinny8<1, 2, 8, false> 256"], ["skinny8<1, 4, 4, false> 1000"]]
+    assert decode(8) == [["dec64x<1, 0, 3> 256"], ["skinny8<1, 2, 8, false> 256"], ["dec64x<1, 0, 8> 172"], ["dec64x<1, 2, 6> 230"], ["skinny8<1, 2, 8, false> 256"], ["dec64x<1, 1, 4> 500"]]
+    assert decode(9) == [["dec64x<1, 0, 3> 256"], ["skinny8<2, 2, 4, false> 256"], ["dec64x<1, 0, 8> 172"], ["dec64x<1, 2, 6> 230"], ["skinny8<2, 2, 4, false> 256"], ["dec64x<1, 1, 4> 500"]]
+    assert decode(16) == [["dec64x<1, 0, 3> 256"], ["skinny8<2, 2, 4, false> 256"], ["dec64x<1, 0, 8> 172"], ["dec64x<1, 2, 6> 230"], ["skinny8<2, 2, 4, false> 256"], ["dec64x<1, 1, 4> 500"]]
+    assert decode(24) == [["dec64x<2, 0, 3> 256"], ["skinny8<3, 2, 2, false> 256"], ["dec64x<2, 0, 8> 172"], ["dec64x<2, 2, 6> 230"], ["skinny8<3, 2, 2, false> 256"], ["dec64x<2, 1, 4> 500"]]
+    assert decode(32) == [["dec64x<2, 0, 3> 256"], ["skinny8<4, 2, 2, false> 256"], ["dec64x<2, 0, 8> 172"], ["dec64x<2, 2, 6> 230"], ["skinny8<4, 2, 2, false> 256"], ["dec64x<2, 1, 4> 500"]]
+    assert decode(33) == [["dec64x<3, 0, 3> 256"], ["skinny<3, 1, 4, false> 256"], ["dec64x<3, 0, 8> 172"], ["dec64x<3, 2, 6> 230"], ["skinny<3, 1, 4, false> 256"], ["dec64x<3, 1, 4> 500"]]
+    assert decode(64) == [["dec64x<4, 0, 3> 256"], ["skinny<4, 1, 4, false> 256"], ["dec64x<4, 0, 8> 172"], ["dec64x<4, 2, 6> 230"], ["skinny<4, 1, 4, false> 256"], ["dec64x<4, 1, 8> 250"]]
+    # the flags the GPU tests cross-check with: gemm_variant 4 / 15 / 17 / 31, use_tr bits 3, 4, 5-6, 7-8, 10, 11, 12 (bits 0 and 3 belong to
+    # gemm_tn and attention, bit 12 to the argument block: the kernels stay)
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=4, tr=1) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=4, tr=1) == ["kernel_x<64, true, 2> 8096"]
+    assert plan(M=24890, N=22016, K1=4096, var=4, tr=1) == ["kernel_x<64, true, 2> 33540"]
+    assert plan(M=2305, N=8192, K1=4096, var=4, tr=1) == ["kernel_x<64, true, 2> 1216"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=4, tr=1) == ["kernel_x<64, true, 2> 3200"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=4, tr=1) == ["w4<false, false, false> 86"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=4, tr=1) == ["kernel_x<64, true, 2> 96"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=4, tr=1) == ["kernel_x<64, true, 2> 32"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=15, tr=1) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=15, tr=1) == ["w4s<true, 0, true> 256"]
+    assert plan(M=24890, N=22016, K1=4096, var=15, tr=1) == ["w4s<false, 0, false> 256"]
+    assert plan(M=2305, N=8192, K1=4096, var=15, tr=1) == ["w4<true, false, false> 256", "kernel_x<64, true, 2> 256"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=15, tr=1) == ["p8 800"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=15, tr=1) == ["skinny8<1, 2, 8, true> 1376"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=15, tr=1) == ["skinny8<3, 2, 2, false> 768"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=15, tr=1) == ["skinny<3, 1, 4, false> 256"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=17, tr=1) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=17, tr=1) == ["p8 2032"]
+    assert plan(M=24890, N=22016, K1=4096, var=17, tr=1) == ["p8 8428"]
+    assert plan(M=2305, N=8192, K1=4096, var=17, tr=1) == ["p8 320"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=17, tr=1) == ["p8 800"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=17, tr=1) == ["w4<false, false, false> 86"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=17, tr=1) == ["p8 48"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=17, tr=1) == ["p8 16"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=31, tr=1) == ["w4<true, false, false> 6096"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=31, tr=1) == ["w4<true, false, true> 2032"]
+    assert plan(M=24890, N=22016, K1=4096, var=31, tr=1) == ["w4<false, false, false> 8428"]
+    assert plan(M=2305, N=8192, K1=4096, var=31, tr=1) == ["w4<true, false, false> 320"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=31, tr=1) == ["w4<true, true, false> 800"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=31, tr=1) == ["w4<false, false, false> 86"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=31, tr=1) == ["w4<true, false, false> 48"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=31, tr=1) == ["w4<true, false, false> 16"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=10, tr=0) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=10, tr=0) == ["w4s<true, 0, true> 256"]
+    assert plan(M=24890, N=22016, K1=4096, var=10, tr=0) == ["w4s<false, 0, false> 256"]
+    assert plan(M=2305, N=8192, K1=4096, var=10, tr=0) == ["w4<true, false, false> 256", "kernel_x<64, true, 2> 256"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=10, tr=0) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=10, tr=0) == ["dec64x<1, 2, 6> 230"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=10, tr=0) == ["dec64x<2, 0, 3> 256"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=10, tr=0) == ["skinny<3, 1, 4, false> 256"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=10, tr=9) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=10, tr=9) == ["w4s<true, 0, true> 256"]
+    assert plan(M=24890, N=22016, K1=4096, var=10, tr=9) == ["w4s<false, 0, false> 256"]
+    assert plan(M=2305, N=8192, K1=4096, var=10, tr=9) == ["w4<true, false, false> 256", "kernel_x<64, true, 2> 256"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=10, tr=9) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=10, tr=9) == ["dec64x<1, 2, 6> 230"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=10, tr=9) == ["dec64x<2, 0, 3> 256"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=10, tr=9) == ["skinny<3, 1, 4, false> 256"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=10, tr=17) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=10, tr=17) == ["w4s<true, 0, true> 256"]
+    assert plan(M=24890, N=22016, K1=4096, var=10, tr=17) == ["w4s<false, 0, false> 256"]
+    assert plan(M=2305, N=8192, K1=4096, var=10, tr=17) == ["w4<true, false, false> 256", "kernel_x<64, true, 2> 256"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=10, tr=17) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=10, tr=17) == ["dec64x<1, 2, 6> 230"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=10, tr=17) == ["dec64x<2, 0, 3> 256"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=10, tr=17) == ["skinny<3, 1, 4, false> 256"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=10, tr=33) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=10, tr=33) == ["w4s<true, 0, true> 256"]
+    assert plan(M=24890, N=22016, K1=4096, var=10, tr=33) == ["w4s<false, 0, false> 256"]
+    assert plan(M=2305, N=8192, K1=4096, var=10, tr=33) == ["w4<true, false, false> 256", "kernel_x<64, true, 2> 256"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=10, tr=33) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=10, tr=33) == ["skinny8<1, 2, 8, true> 1376"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=10, tr=33) == ["skinny8<3, 2, 2, false> 768"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=10, tr=33) == ["skinny<3, 1, 4, false> 256"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=10, tr=65) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=10, tr=65) == ["w4s<true, 0, true> 256"]
+    assert plan(M=24890, N=22016, K1=4096, var=10, tr=65) == ["w4s<false, 0, false> 256"]
+    assert plan(M=2305, N=8192, K1=4096, var=10, tr=65) == ["w4<true, false, false> 256", "kernel_x<64, true, 2> 256"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=10, tr=65) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=10, tr=65) == ["dec64<1, 2, 4, 1> 344"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=10, tr=65) == ["dec64<2, 0, 4, 2> 384"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=10, tr=65) == ["skinny<3, 1, 4, false> 256"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=10, tr=97) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=10, tr=97) == ["w4s<true, 0, true> 256"]
+    assert plan(M=24890, N=22016, K1=4096, var=10, tr=97) == ["w4s<false, 0, false> 256"]
+    assert plan(M=2305, N=8192, K1=4096, var=10, tr=97) == ["w4<true, false, false> 256", "kernel_x<64, true, 2> 256"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=10, tr=97) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=10, tr=97) == ["dec64x<1, 2, 6> 230"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=10, tr=97) == ["dec64x<2, 0, 3> 256"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=10, tr=97) == ["skinny<3, 1, 4, false> 256"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=10, tr=129) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=10, tr=129) == ["w4s<true, 0, true> 256"]
+    assert plan(M=24890, N=22016, K1=4096, var=10, tr=129) == ["w4s<false, 0, false> 256"]
+    assert plan(M=2305, N=8192, K1=4096, var=10, tr=129) == ["w4<true, false, false> 256", "kernel_x<64, true, 2> 256"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=10, tr=129) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=10, tr=129) == ["dec64x<1, 2, 6> 230"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=10, tr=129) == ["dec64x<2, 0, 3> 256"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=10, tr=129) == ["skinny<3, 1, 4, false> 256"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=10, tr=257) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=10, tr=257) == ["w4s<true, 0, true> 256"]
+    assert plan(M=24890, N=22016, K1=4096, var=10, tr=257) == ["w4s<false, 0, false> 256"]
+    assert plan(M=2305, N=8192, K1=4096, var=10, tr=257) == ["w4<true, false, false> 256", "kernel_x<64, true, 2> 256"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=10, tr=257) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=10, tr=257) == ["dec64x<1, 2, 4> 344"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=10, tr=257) == ["dec64x<2, 0, 4> 192"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=10, tr=257) == ["skinny<3, 1, 4, false> 256"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=10, tr=385) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=10, tr=385) == ["w4s<true, 0, true> 256"]
+    assert plan(M=24890, N=22016, K1=4096, var=10, tr=385) == ["w4s<false, 0, false> 256"]
+    assert plan(M=2305, N=8192, K1=4096, var=10, tr=385) == ["w4<true, false, false> 256", "kernel_x<64, true, 2> 256"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=10, tr=385) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=10, tr=385) == ["dec64x<1, 2, 8> 172"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=10, tr=385) == ["dec64x<2, 0, 8> 96"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=10, tr=385) == ["skinny<3, 1, 4, false> 256"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=10, tr=1025) == ["w4s<true, 3, false> 8"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=10, tr=1025) == ["w4s<true, 0, true> 8"]
+    assert plan(M=24890, N=22016, K1=4096, var=10, tr=1025) == ["w4s<false, 0, false> 8"]
+    assert plan(M=2305, N=8192, K1=4096, var=10, tr=1025) == ["w4s<true, 0, false> 8", "kernel_x<64, true, 2> 256"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=10, tr=1025) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=10, tr=1025) == ["dec64x<1, 2, 6> 230"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=10, tr=1025) == ["dec64x<2, 0, 3> 256"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=10, tr=1025) == ["skinny<3, 1, 4, false> 256"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=10, tr=2049) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=10, tr=2049) == ["w4<true, false, false> 2032"]
+    assert plan(M=24890, N=22016, K1=4096, var=10, tr=2049) == ["w4s<false, 0, false> 256"]
+    assert plan(M=2305, N=8192, K1=4096, var=10, tr=2049) == ["w4<true, false, false> 256", "kernel_x<64, true, 2> 256"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=10, tr=2049) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=10, tr=2049) == ["dec64x<1, 2, 6> 230"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=10, tr=2049) == ["dec64x<2, 0, 3> 256"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=10, tr=2049) == ["skinny<3, 1, 4, false> 256"]
+    assert plan(M=32362, N=12288, K1=4096, K2=768, a2g=4096, a2s=256, rope=2, var=10, tr=4097) == ["w4s<true, 3, false> 256"]
+    assert plan(M=32362, N=4096, K1=11008, K2=256, out_f32=1, R=1, var=10, tr=4097) == ["w4s<true, 0, true> 256"]
+    assert plan(M=24890, N=22016, K1=4096, var=10, tr=4097) == ["w4s<false, 0, false> 256"]
+    assert plan(M=2305, N=8192, K1=4096, var=10, tr=4097) == ["w4<true, false, false> 256", "kernel_x<64, true, 2> 256"]
+    assert plan(M=12694, N=4096, K1=1024, bias=1, act=1, var=10, tr=4097) == ["w4<true, true, false> 768", "tail64<4> 512"]
+    assert plan(M=8, N=22016, K1=4096, act=S | 3, ldc=11008, var=10, tr=4097) == ["dec64x<1, 2, 6> 230"]
+    assert plan(M=24, N=12288, K1=4096, act=S, var=10, tr=4097) == ["dec64x<2, 0, 3> 256"]
+    assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=10, tr=4097) == ["skinny<3, 1, 4, false> 256"]
+
+
 def test_generated_kloop_is_current():
     """opa-dpo_amd/csrc/w4_kloop.inc (the K-loop of gemm_nt_w4_kernel as an asm block) is generated: the committed file must be what the
     committed generator emits, and the generator's hazard checks (LDS stage reuse, fragment registers, M0, vmcnt bookkeeping) must hold."""
