@@ -322,9 +322,10 @@ int opadpo_ctx_create(const opadpo_dims* dims, int device, opadpo_ctx** out);
 void opadpo_ctx_destroy(opadpo_ctx* ctx);
 const char* opadpo_ctx_last_error(const opadpo_ctx* ctx);
 int opadpo_ctx_set_allocator(opadpo_ctx* ctx, opadpo_alloc_fn alloc, opadpo_free_fn free_fn, void* user);
-/* gemm_variant as in opadpo_set_flags, for this context only; -1 = process default.  use_tr is a SEPARATE bit space from the process flags: only
- * bits 0-4 mean what they mean in opadpo_set_flags (passed on to the kernels of this context); bits 5-14 are the context switches listed here
- * (process bits 5-10 - decode GEMM kernel, sampler sweep, 8-workgroup walk - have no per-context form and are NOT read from this value).
+/* gemm_variant as in opadpo_set_flags, for this context only; -1 = process default.  use_tr is a SEPARATE bit space from the process flags.
+ * use_tr = -1: the context's attention and gemm_tn kernels follow the process flags (later opadpo_set_flags calls included).  use_tr >= 0: its
+ * bit 0 (transposed LDS reads) and bit 3 (128x128 gemm_tn) replace process bits 0 and 3 for this context; bits 1, 2 and 4 are NOT read (the
+ * attention DMA forward and the skinny8 choice stay with the process flags, as do process bits 5-12); bits 5-14 are the context switches listed here.
  * Context bits: use_tr bit 5 = keep the
  * 16/32-row streaming GEMMs for rollouts of 33..64 sequences (default there: the LDS-ring decode GEMM, opadpo_gemm_nt_decode);
  * bit 6 = SwiGLU backward in the LDS-STAGED epilogue of the down projection's dgrad (the form of rounds 3-4, which measured 0.35 % slower per step
@@ -341,10 +342,10 @@ int opadpo_ctx_set_allocator(opadpo_ctx* ctx, opadpo_alloc_fn alloc, opadpo_free
  * bit 13 = residual adds of the full-sequence passes deferred to the RMSNorm that follows (rmsnorm_sum_fwd: x = res + y, 14 B per element; the form of
  *   rounds 2-4).  Default since round 5: the o / down projections add their fp32 residual rows in the 256x256 kernels' DIRECT epilogue (rows requested
  *   one row block ahead of the accumulator read-out) and the norm pass reads 6 B per element - the same fp32 addition of the same operands, so h / x
- *   keep their bits; -1.0 % per step.  OPADPO_FUSE_RESID=0 makes the deferred form the process default (A/B runs).
+ *   keep their bits; -1.0 % per step.
  * bit 14 = SwiGLU backward as its own kernel (silu_mul_bwd; rounds 1-4).  Default since round 5: inside the direct epilogue of the down projection's
  *   dgrad (OPADPO_ACT_SWIGLU_BWD, gate / up operands requested one row block ahead; bit-identical to the two-kernel form, d_act never reaches HBM;
- *   -0.8 % per step); bit 6 selects the LDS-staged form of that epilogue (rounds 3-4; cross-check).  OPADPO_FUSE_SWIGLU_BWD=0: process default off. */
+ *   -0.8 % per step); bit 6 selects the LDS-staged form of that epilogue (rounds 3-4; cross-check). */
 int opadpo_ctx_set_flags(opadpo_ctx* ctx, int gemm_variant, int use_tr);
 /* how the LAST opadpo_seq_logprobs_bwd of this context flushed its LoRA wgrads: 1 = ordered reduce (bit-reproducible), 0 = fp32 atomics
  * (bit 12 set, or lora_r % 256 != 0), -1 = no backward yet */

@@ -1374,82 +1374,112 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq32_kernel(AttnArgs p) {
 
 }  // namespace
 
-static bool g_attn_dma = false;   // measured: the 64-KiB ring allows 2 blocks/CU, the 32-KiB register-staged kernel 3 -> 0.92 vs 1.01 ms
-void opadpo_set_attn_dma(bool on) { g_attn_dma = on; }
+// ==== attention dispatch: a pure plan of at most three launches from (arguments, flags), then one loop that launches it ================
+namespace {
+struct AttnKernel { const char* name; const void* fn; int lds; };      // every kernel: 256 threads, one AttnArgs parameter
+#define AK(LDS, ...) {#__VA_ARGS__, (const void*)__VA_ARGS__, LDS}
+#define AK_FWD(HD, TR, DMA) AK((DMA ? 4 : 2) * 64 * HD * 2 + (DMA ? 160 : 80), attn_fwd_kernel<HD, TR, DMA>)
+// positions in the kernel table (below, same order); hd = 0 / 1 for head_dim 128 / 64
+enum : int {
+  A_FWD32, A_DQ32,
+  A_FWD,                 // + 4 * hd + 2 * !tr + !dma
+  A_DELTA = A_FWD + 8,   // + hd
+  A_DKDV = A_DELTA + 2,  // + 2 * hd + !tr
+  A_DQ = A_DKDV + 4,     // + 2 * hd + !tr
+  A_COUNT = A_DQ + 4
+};
+const AttnKernel g_attn_kernels[] = {
+  AK(4 * 64 * 128 * 2 + 160, attn_fwd32_kernel), AK(4 * 64 * 128 * 2 + 160, attn_bwd_dq32_kernel),
+  AK_FWD(128, true, true), AK_FWD(128, true, false), AK_FWD(128, false, true), AK_FWD(128, false, false),
+  AK_FWD(64, true, true), AK_FWD(64, true, false), AK_FWD(64, false, true), AK_FWD(64, false, false),
+  AK(0, attn_delta_kernel<128>), AK(0, attn_delta_kernel<64>),
+  AK(4 * 64 * 128 * 2 + 1024 + 80 + 64, attn_bwd_dkdv_kernel<128, true>), AK(4 * 64 * 128 * 2 + 1024 + 80 + 64, attn_bwd_dkdv_kernel<128, false>),
+  AK(4 * 64 * 64 * 2 + 1024 + 80 + 64, attn_bwd_dkdv_kernel<64, true>), AK(4 * 64 * 64 * 2 + 1024 + 80 + 64, attn_bwd_dkdv_kernel<64, false>),
+  AK(0, attn_bwd_dq_kernel<128, true>), AK(0, attn_bwd_dq_kernel<128, false>), AK(0, attn_bwd_dq_kernel<64, true>), AK(0, attn_bwd_dq_kernel<64, false>),
+};
+#undef AK_FWD
+#undef AK
+static_assert(sizeof(g_attn_kernels) / sizeof(g_attn_kernels[0]) == A_COUNT, "kernel table and its positions disagree");
+bool g_attn_attr[A_COUNT];      // the dynamic-LDS attribute was set (the first launch of each kernel)
 
-static int g_attn32 = -1;         // 1 (default): head_dim-128 forward on the 32-rows-per-wave kernel; OPADPO_ATTN32=0 keeps the 16-row kernel (A/B)
-hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t st) {
+struct AttnPlan {
+  int n = 0;
+  int kernel[3];
+  unsigned grid[3];
+  void add(int k, size_t g) { kernel[n] = k; grid[n++] = (unsigned)g; }
+};
+
+hipError_t plan_attn_fwd(const AttnArgs& a, const KernelFlags& f, AttnPlan& p) {
   if (a.S <= 0 || a.L <= 0) return hipSuccess;
   if (a.hd != 128 && a.hd != 64) return hipErrorInvalidValue;
-  if (g_attn32 < 0) { const char* v = getenv("OPADPO_ATTN32"); g_attn32 = (v && v[0] == '0') ? 0 : 1; }
-  const bool legacy = a.use_tr >= 0 && (a.use_tr & 256);      // per-call: context flag bit 8 = the 16-row forward kernel
-  if (a.hd == 128 && g_attn32 && !legacy && (double)a.L * a.ld * 2 < 2.0e9) {
-    static bool attr32 = false;
-    if (!attr32) { (void)hipFuncSetAttribute((const void*)attn_fwd32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 128 * 2 + 160); attr32 = true; }
-    const dim3 grid32((unsigned)(((a.L + 127) / 128) * a.nh * a.S));
-    hipLaunchKernelGGL(attn_fwd32_kernel, grid32, dim3(256), 4 * 64 * 128 * 2 + 160, st, a);
-    return hipGetLastError();
+  const bool fit32 = (double)a.L * a.ld * 2 < 2.0e9;      // per-sequence extent must fit a 32-bit descriptor
+  // head_dim 128: the 32-rows-per-wave kernel; context flag bit 8 keeps the 16-row one
+  if (a.hd == 128 && !f.attn_rows16 && fit32) {
+    p.add(A_FWD32, (size_t)((a.L + 127) / 128) * a.nh * a.S);
+    return hipSuccess;
   }
-  const dim3 grid((unsigned)(((a.L + 63) / 64) * a.nh * a.S));
-  const bool tr = a.use_tr >= 0 ? (a.use_tr & 1) != 0 : opadpo_flag_tr();
-  const bool dma = g_attn_dma && (double)a.L * a.ld * 2 < 2.0e9;     // per-sequence extent must fit the 32-bit descriptor
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<128, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 128 * 2 + 160);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<128, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 128 * 2 + 160);
-    attr_set = true;
-  }
-#define FWD(HD_, TR_, DMA_) hipLaunchKernelGGL((attn_fwd_kernel<HD_, TR_, DMA_>), grid, dim3(256), (DMA_ ? 4 : 2) * 64 * HD_ * 2 + (DMA_ ? 160 : 80), st, a)
-  if (a.hd == 128) {
-    if (tr) { if (dma) FWD(128, true, true); else FWD(128, true, false); }
-    else    { if (dma) FWD(128, false, true); else FWD(128, false, false); }
-  } else {
-    if (tr) { if (dma) FWD(64, true, true); else FWD(64, true, false); }
-    else    { if (dma) FWD(64, false, true); else FWD(64, false, false); }
-  }
-#undef FWD
-  return hipGetLastError();
+  // LDS-DMA K/V ring (process flag bit 1).  Measured: the 64-KiB ring allows 2 blocks/CU, the 32-KiB register-staged kernel 3 -> 0.92 vs 1.01 ms
+  const bool dma = f.attn_dma && fit32;
+  p.add(A_FWD + 4 * (a.hd == 64) + 2 * !f.use_tr + !dma, (size_t)((a.L + 63) / 64) * a.nh * a.S);
+  return hipSuccess;
 }
 
-hipError_t launch_attn_bwd(const AttnArgs& a, hipStream_t st) {
+hipError_t plan_attn_bwd(const AttnArgs& a, const KernelFlags& f, AttnPlan& p) {
   if (a.S <= 0 || a.L <= 0) return hipSuccess;
   if (a.hd != 128 && a.hd != 64) return hipErrorInvalidValue;
-  const int total = (a.seq_meta ? a.rows_total : a.S * a.L) * a.nh;
-  const dim3 grid((unsigned)(((a.L + 63) / 64) * a.nh * a.S));
-  const bool tr = a.use_tr >= 0 ? (a.use_tr & 1) != 0 : opadpo_flag_tr();
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 128 * 2 + 1024 + 80 + 64);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 128 * 2 + 1024 + 80 + 64);
-    attr_set = true;
-  }
   if ((double)a.L * a.ld * 2 >= 2.0e9 || (double)a.L * a.ldo * 2 >= 2.0e9) return hipErrorInvalidValue;   // 32-bit buffer extents
-  static int g_dq32 = -1;
-  if (g_dq32 < 0) {
-    const char* v = getenv("OPADPO_DQ32");
-    g_dq32 = (v && v[0] == '0') ? 0 : 1;      // default: the 32-rows-per-wave dQ kernel at head_dim 128 (bf16 dQ, no fp32 copy); OPADPO_DQ32=0 / context flag bit 8 keep the 16-row kernel
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 128 * 2 + 160);
+  const int hd64 = a.hd == 64, total = (a.seq_meta ? a.rows_total : a.S * a.L) * a.nh;
+  const size_t tiles = (size_t)((a.L + 63) / 64) * a.nh * a.S;
+  p.add(A_DELTA + hd64, (total + 4 * (512 / a.hd) - 1) / (4 * (512 / a.hd)));
+  p.add(A_DKDV + 2 * hd64 + !f.use_tr, tiles);
+  // dQ at head_dim 128: the 32-rows-per-wave kernel (bf16 dQ, no fp32 copy); context flag bit 8 keeps the 16-row one
+  if (!hd64 && a.dq && !a.dq_acc && !f.attn_rows16) p.add(A_DQ32, (size_t)((a.L + 127) / 128) * a.nh * a.S);
+  else p.add(A_DQ + 2 * hd64 + !f.use_tr, tiles);
+  return hipSuccess;
+}
+
+hipError_t launch_attn_plan(const AttnPlan& p, const AttnArgs& a, hipStream_t st) {
+  AttnArgs args = a;
+  void* kargs[] = {&args};
+  for (int i = 0; i < p.n; ++i) {
+    const AttnKernel& k = g_attn_kernels[p.kernel[i]];
+    set_lds_once(g_attn_attr[p.kernel[i]], k.fn, k.lds);
+    if (hipLaunchKernel(k.fn, dim3(p.grid[i]), dim3(256), kargs, k.lds, st) != hipSuccess) break;
   }
-  const bool dq32 = g_dq32 && a.dq && !a.dq_acc && !(a.use_tr >= 0 && (a.use_tr & 256));
-#define LAUNCH_BWD(HD_, TR_)                                                                              \
-  hipLaunchKernelGGL((attn_delta_kernel<HD_>), dim3((unsigned)((total + 4 * (512 / HD_) - 1) / (4 * (512 / HD_)))), dim3(256), 0, st, a); \
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HD_, TR_>), grid, dim3(256), 4 * 64 * HD_ * 2 + 1024 + 80 + 64, st, a); \
-  if (HD_ == 128 && dq32) hipLaunchKernelGGL(attn_bwd_dq32_kernel, dim3((unsigned)(((a.L + 127) / 128) * a.nh * a.S)), dim3(256), 4 * 64 * 128 * 2 + 160, st, a); \
-  else hipLaunchKernelGGL((attn_bwd_dq_kernel<HD_, TR_>), grid, dim3(256), 0, st, a)
-  if (a.hd == 128) {
-    if (tr) { LAUNCH_BWD(128, true); } else { LAUNCH_BWD(128, false); }
-  } else {
-    if (tr) { LAUNCH_BWD(64, true); } else { LAUNCH_BWD(64, false); }
-  }
-#undef LAUNCH_BWD
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_attn_fwd(const AttnArgs& a, const KernelFlags& f, hipStream_t st) {
+  AttnPlan p;
+  const hipError_t e = plan_attn_fwd(a, f, p);
+  return e != hipSuccess ? e : launch_attn_plan(p, a, st);
+}
+hipError_t launch_attn_bwd(const AttnArgs& a, const KernelFlags& f, hipStream_t st) {
+  AttnPlan p;
+  const hipError_t e = plan_attn_bwd(a, f, p);
+  return e != hipSuccess ? e : launch_attn_plan(p, a, st);
+}
+hipError_t attn_plan_text(const AttnArgs& a, int backward, const KernelFlags& f, char* out, size_t out_len) {
+  AttnPlan p;
+  const hipError_t e = backward ? plan_attn_bwd(a, f, p) : plan_attn_fwd(a, f, p);
+  if (e != hipSuccess) return e;
+  size_t used = 0;
+  if (out_len) out[0] = 0;
+  for (int i = 0; i < p.n; ++i) {
+    const AttnKernel& k = g_attn_kernels[p.kernel[i]];
+    const int w = snprintf(out + used, out_len - used, "%s %u 256 %d\n", k.name, p.grid[i], k.lds);
+    if (w < 0 || (size_t)w >= out_len - used) return hipErrorInvalidValue;
+    used += w;
+  }
+  return hipSuccess;
 }
 
 // ---- test entry points (not part of the ABI in include/opadpo_hip.h) ----------------------------------------------------------------------
 // opadpo_attn_fwd / _bwd with the fields only opadpo_ctx reaches: ragged rows (seq_meta, meta_stride, n_seg, rows_total; see AttnArgs), the
-// backward's fused inverse rotary embedding (rope_pos, rope_l2theta) and the per-call kernel switch use_tr (-1 = process default; bit 0 =
-// transposed LDS reads, bit 8 = the 16-row forward and dQ kernels, as context flag bit 8).  Every argument is checked before any launch; the
-// metadata is read back to the host for that (the call synchronises its stream).
+// backward's fused inverse rotary embedding (rope_pos, rope_l2theta) and the kernel flags of a context: use_tr is an opadpo_ctx_set_flags word
+// (-1 = none), applied to the process flags as a context's (resolve_flags).  Every argument is checked before any launch; the metadata is read
+// back to the host for that (the call synchronises its stream).
 namespace {
 int attn_debug_check(const char* fn, const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* o, int ld, int ldo, int S_, int L,
                      int nh, int hd, int causal, int seg_prefix, int seg_len, const int32_t* seq_meta, int meta_stride, int n_seg, int rows_total,
@@ -1494,9 +1524,9 @@ extern "C" int opadpo_debug_attn_fwd(const uint16_t* q, const uint16_t* k, const
   memset(&a, 0, sizeof(a));
   a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse; a.key_mask = key_mask;
   a.S = S_; a.L = L; a.nh = nh; a.hd = hd; a.ld = ld; a.ldo = ldo; a.causal = causal; a.scale = scale;
-  a.seg_prefix = seg_prefix; a.seg_len = seg_len; a.use_tr = use_tr;
+  a.seg_prefix = seg_prefix; a.seg_len = seg_len;
   if (seq_meta) { a.seq_meta = seq_meta; a.meta_stride = meta_stride; a.n_seg = n_seg; a.rows_total = rows_total; }
-  return opadpo_report_done(launch_attn_fwd(a, (hipStream_t)stream), fn);
+  return opadpo_report_done(launch_attn_fwd(a, resolve_flags(process_flags(), kernel_overrides(-1, use_tr)), (hipStream_t)stream), fn);
 }
 
 extern "C" int opadpo_debug_attn_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, int ld, const uint16_t* o, const uint16_t* dout,
@@ -1513,8 +1543,26 @@ extern "C" int opadpo_debug_attn_bwd(const uint16_t* q, const uint16_t* k, const
   a.q = q; a.k = k; a.v = v; a.o = (uint16_t*)o; a.lse = (float*)lse; a.key_mask = key_mask;
   a.S = S_; a.L = L; a.nh = nh; a.hd = hd; a.ld = ld; a.ldo = ldo; a.causal = causal; a.scale = scale;
   a.dout = dout; a.dq_acc = dq_f32; a.dq = dq; a.dk = dk; a.dv = dv; a.delta = delta;
-  a.seg_prefix = seg_prefix; a.seg_len = seg_len; a.use_tr = use_tr;
+  a.seg_prefix = seg_prefix; a.seg_len = seg_len;
   if (seq_meta) { a.seq_meta = seq_meta; a.meta_stride = meta_stride; a.n_seg = n_seg; a.rows_total = rows_total; }
   a.rope_pos = rope_pos; a.rope_l2theta = rope_l2theta;
-  return opadpo_report_done(launch_attn_bwd(a, (hipStream_t)stream), fn);
+  return opadpo_report_done(launch_attn_bwd(a, resolve_flags(process_flags(), kernel_overrides(-1, use_tr)), (hipStream_t)stream), fn);
+}
+
+// the launches opadpo_debug_attn_fwd (backward = 0) or _bwd would make, as text (one line per launch: kernel grid.x block LDS); nothing is
+// launched and no operand is read.  rows_total > 0: ragged rows; dq / dq_f32: whether those outputs are given; use_tr: the process word of
+// opadpo_set_flags; ctx_use_tr: an opadpo_ctx_set_flags word (-1 = none)
+extern "C" int opadpo_debug_attn_plan(int S_, int L, int nh, int hd, int ld, int ldo, int rows_total, int backward, int dq, int dq_f32, int use_tr,
+                                      int ctx_use_tr, char* out, int out_len) {
+  if (!out || out_len <= 0) return opadpo_report_bad("opadpo_debug_attn_plan", "output buffer");
+  static const int32_t meta = 0;
+  static uint16_t dq_buf;
+  static float dq_f32_buf;
+  AttnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.S = S_; a.L = L; a.nh = nh; a.hd = hd; a.ld = ld; a.ldo = ldo;
+  if (rows_total > 0) { a.seq_meta = &meta; a.rows_total = rows_total; }
+  a.dq = dq ? &dq_buf : nullptr; a.dq_acc = dq_f32 ? &dq_f32_buf : nullptr;
+  const KernelFlags f = resolve_flags(kernel_flags(10, use_tr), kernel_overrides(-1, ctx_use_tr));
+  return opadpo_report_done(attn_plan_text(a, backward, f, out, (size_t)out_len), "opadpo_debug_attn_plan");
 }

@@ -20,6 +20,8 @@ int bad(const char* where, const char* what) {
 inline int done(hipError_t e, const char* where) { return e == hipSuccess ? 0 : fail(e, where); }
 inline hipStream_t S(void* s) { return (hipStream_t)s; }
 
+KernelFlags g_flags;      // opadpo_set_flags
+
 // opadpo_gemm_nt's validation and argument block
 int gemm_nt_args(GemmNTArgs& a, const char* fn, const uint16_t* A1, int lda1, const uint16_t* B1, int ldb1, int K1,
                  const uint16_t* A2, int lda2, const uint16_t* B2, int ldb2, int K2, int a2_group_n, int a2_group_stride, int a1_group_n, int a1_group_stride,
@@ -45,16 +47,48 @@ int gemm_nt_args(GemmNTArgs& a, const char* fn, const uint16_t* A1, int lda1, co
 hipError_t gemm_nt_op(const GemmNTArgs& a, hipStream_t st) {
   static void* ws = nullptr;
   static size_t ws_bytes = 0;
-  const size_t need = gemm_nt_workspace_bytes(a);
+  const size_t need = gemm_nt_workspace_bytes(a, g_flags);
   if (need > ws_bytes) {
     if (ws) (void)hipFree(ws);
     ws = nullptr; ws_bytes = 0;
     if (hipMalloc(&ws, need + need / 4) != hipSuccess) { (void)hipGetLastError(); return hipErrorOutOfMemory; }
     ws_bytes = need + need / 4;
   }
-  return launch_gemm_nt(a, st, ws, ws_bytes);
+  return launch_gemm_nt(a, g_flags, st, ws, ws_bytes);
 }
 }  // namespace
+
+KernelFlags kernel_flags(int gemm_variant, int use_tr) {
+  KernelFlags f;
+  f.variant = gemm_variant;
+  f.use_tr = (use_tr & 1) != 0;
+  f.attn_dma = (use_tr & 2) != 0;
+  f.tn_w4 = (use_tr & 8) == 0;
+  f.skinny8 = (use_tr & 16) == 0;
+  f.dec64_variant = (use_tr >> 5) & 3;
+  f.dec64x_nw = (use_tr >> 7) & 3;
+  f.sample_compact = (use_tr & 512) == 0;
+  f.w4s_few = (use_tr & 1024) != 0;
+  f.w4_nodeep = (use_tr & 2048) != 0;
+  f.w4_chunk_deal = (use_tr & 4096) != 0;
+  return f;
+}
+const KernelFlags& process_flags() { return g_flags; }
+KernelOverrides kernel_overrides(int gemm_variant, int use_tr) {
+  KernelOverrides o;
+  o.gemm_variant = gemm_variant;
+  o.word = use_tr >= 0;
+  o.use_tr = o.word && (use_tr & 1);
+  o.tn_w4 = o.word && !(use_tr & 8);
+  o.attn_rows16 = o.word && (use_tr & 256);
+  return o;
+}
+KernelFlags resolve_flags(const KernelFlags& process, const KernelOverrides& o) {
+  KernelFlags f = process;
+  if (o.gemm_variant >= 0) f.variant = o.gemm_variant;
+  if (o.word) { f.use_tr = o.use_tr; f.tn_w4 = o.tn_w4; f.attn_rows16 = o.attn_rows16; }
+  return f;
+}
 
 // the same reporting for extern "C" entry points that live in other translation units (kernels.h)
 int opadpo_report_bad(const char* where, const char* what) { return bad(where, what); }
@@ -64,7 +98,7 @@ extern "C" {
 
 int opadpo_abi_version(void) { return OPADPO_ABI_VERSION; }
 const char* opadpo_last_error(void) { return g_err; }
-void opadpo_set_flags(int use_glds, int use_tr) { opadpo_set_flags_impl(use_glds, use_tr); }
+void opadpo_set_flags(int use_glds, int use_tr) { g_flags = kernel_flags(use_glds, use_tr); }
 
 int opadpo_gemm_nt(const uint16_t* A1, int lda1, const uint16_t* B1, int ldb1, int K1,
                    const uint16_t* A2, int lda2, const uint16_t* B2, int ldb2, int K2,
@@ -96,7 +130,7 @@ int opadpo_debug_gemm_nt_plan(const uint16_t* A1, int lda1, const uint16_t* B1, 
   a.rope_cols = rope ? N : 0;
   if (rope == 1) { a.rope_cos = &tab; a.rope_sin = &tab; a.rope_L = 4096; }
   if (rope == 2) { a.rope_pos = &pos; a.rope_l2theta = log2f(10000.f); }
-  return done(gemm_nt_plan_text(a, gemm_variant, use_tr, cus, out, (size_t)out_len), fn);
+  return done(gemm_nt_plan_text(a, kernel_flags(gemm_variant, use_tr), cus, out, (size_t)out_len), fn);
 }
 
 int opadpo_gemm_nt_rope(const uint16_t* A1, int lda1, const uint16_t* B1, int ldb1, int K1,
@@ -148,9 +182,9 @@ int opadpo_gemm_nt_decode(const uint16_t* A, int lda, const uint16_t* B, int ldb
   a.A1 = A; a.B1 = B; a.A2 = nullptr; a.B2 = nullptr; a.C = C; a.R = nullptr; a.bias = nullptr;
   a.M = M; a.N = N; a.K1 = K; a.K2 = 0; a.lda1 = lda; a.ldb1 = ldb; a.lda2 = 0; a.ldb2 = 0; a.ldc = ldc; a.ldr = 0;
   a.a2_group_n = 0; a.a2_group_stride = 0; a.a1_group_n = 0; a.a1_group_stride = 0; a.alpha = 1.f; a.act = 0; a.out_f32 = mode == 1; a.r_f32 = 0;
-  return done(launch_gemm_nt_dec64(a, mode, splits, S(stream)), "opadpo_gemm_nt_decode");
+  return done(launch_gemm_nt_dec64(a, mode, splits, g_flags, S(stream)), "opadpo_gemm_nt_decode");
 }
-int opadpo_gemm_nt_decode_splits(int N, int K, int splits) { return (N > 0 && K >= 64) ? gemm_nt_dec64_splits(N, K, splits) : 1; }
+int opadpo_gemm_nt_decode_splits(int N, int K, int splits) { return (N > 0 && K >= 64) ? gemm_nt_dec64_splits(N, K, splits, g_flags) : 1; }
 int opadpo_rmsnorm_sum_fwd(const void* resid, int resid_f32, const float* partials, int n_partials, size_t partial_stride, const uint16_t* w,
                            float* x_out, uint16_t* y, float* rstd, int rows, int H, float eps, void* stream) {
   if (!resid || !w || !x_out) return bad("opadpo_rmsnorm_sum_fwd", "null operand");
@@ -166,7 +200,7 @@ int opadpo_gemm_tn(const uint16_t* P, int ldp, const uint16_t* Q, int ldq, float
   GemmTNArgs a;
   a.P = P; a.Q = Q; a.C = C; a.M = M; a.N1 = N1; a.N2 = N2; a.ldp = ldp; a.ldq = ldq; a.ldc = ldc;
   a.q_group_n1 = q_group_n1; a.q_group_stride = q_group_stride; a.alpha = alpha; a.splits = splits;
-  return done(launch_gemm_tn(a, S(stream)), "opadpo_gemm_tn");
+  return done(launch_gemm_tn(a, g_flags, S(stream)), "opadpo_gemm_tn");
 }
 
 int opadpo_gemm_tn_group(int n, const uint16_t* const* P, const int* ldp, const uint16_t* const* Q, const int* ldq, float* const* C, const int* ldc,
@@ -181,7 +215,7 @@ int opadpo_gemm_tn_group(int n, const uint16_t* const* P, const int* ldp, const 
     a.q_group_n1 = q_group_n1 ? q_group_n1[i] : 0; a.q_group_stride = q_group_stride ? q_group_stride[i] : 0; a.alpha = alpha; a.splits = 0;
     if (a.q_group_n1 && a.q_group_n1 % 128) return bad("opadpo_gemm_tn_group", "q_group_n1 must be a multiple of 128");
   }
-  return done(launch_gemm_tn_group(list, n, S(stream)), "opadpo_gemm_tn_group");
+  return done(launch_gemm_tn_group(list, n, g_flags, S(stream)), "opadpo_gemm_tn_group");
 }
 
 static int tn_group_list(const char* fn, GemmTNArgs* list, int n, const uint16_t* const* P, const int* ldp, const uint16_t* const* Q, const int* ldq, float* const* C,
@@ -203,7 +237,7 @@ static int tn_group_list(const char* fn, GemmTNArgs* list, int n, const uint16_t
 size_t opadpo_gemm_tn_group_workspace_bytes(int n, int M, const int* N1, const int* N2, const int* q_group_n1) {
   GemmTNArgs list[8];
   if (M <= 0 || tn_group_list("opadpo_gemm_tn_group_workspace_bytes", list, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, M, N1, N2, q_group_n1, nullptr, 1.f, true)) return 0;
-  return gemm_tn_group_workspace_bytes(list, n);
+  return gemm_tn_group_workspace_bytes(list, n, g_flags);
 }
 
 int opadpo_gemm_tn_group_det(int n, const uint16_t* const* P, const int* ldp, const uint16_t* const* Q, const int* ldq, float* const* C, const int* ldc,
@@ -211,10 +245,10 @@ int opadpo_gemm_tn_group_det(int n, const uint16_t* const* P, const int* ldp, co
                              void* workspace, size_t workspace_bytes, void* stream) {
   GemmTNArgs list[8];
   if (const int rc = tn_group_list("opadpo_gemm_tn_group_det", list, n, P, ldp, Q, ldq, C, ldc, M, N1, N2, q_group_n1, q_group_stride, alpha, false)) return rc;
-  const size_t need = gemm_tn_group_workspace_bytes(list, n);
+  const size_t need = gemm_tn_group_workspace_bytes(list, n, g_flags);
   if (need == 0) return bad("opadpo_gemm_tn_group_det", "these problems do not run on the 256x256 kernel (N1, N2, q_group_n1 % 256): no deterministic form");
   if (!workspace || workspace_bytes < need) return bad("opadpo_gemm_tn_group_det", "workspace smaller than opadpo_gemm_tn_group_workspace_bytes");
-  return done(launch_gemm_tn_group(list, n, S(stream), workspace, workspace_bytes), "opadpo_gemm_tn_group_det");
+  return done(launch_gemm_tn_group(list, n, g_flags, S(stream), workspace, workspace_bytes), "opadpo_gemm_tn_group_det");
 }
 
 int opadpo_attn_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, int ld, uint16_t* o, int ldo,
@@ -228,8 +262,8 @@ int opadpo_attn_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, int
   a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse; a.key_mask = key_mask;
   a.S = S_; a.L = L; a.nh = nh; a.hd = hd; a.ld = ld; a.ldo = ldo; a.causal = causal; a.scale = scale;
   if (seg_len < 0 || seg_prefix < 0 || (seg_len > 0 && !causal)) return bad("opadpo_attn_fwd", "packed responses need causal attention and seg_prefix, seg_len >= 0");
-  a.seg_prefix = seg_prefix; a.seg_len = seg_len; a.use_tr = -1;
-  return done(launch_attn_fwd(a, S(stream)), "opadpo_attn_fwd");
+  a.seg_prefix = seg_prefix; a.seg_len = seg_len;
+  return done(launch_attn_fwd(a, g_flags, S(stream)), "opadpo_attn_fwd");
 }
 
 int opadpo_attn_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, int ld, const uint16_t* o,
@@ -245,8 +279,8 @@ int opadpo_attn_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, int
   a.q = q; a.k = k; a.v = v; a.o = (uint16_t*)o; a.lse = (float*)lse; a.key_mask = key_mask;
   a.S = S_; a.L = L; a.nh = nh; a.hd = hd; a.ld = ld; a.ldo = ldo; a.causal = causal; a.scale = scale;
   a.dout = dout; a.dq_acc = dq_f32; a.dq = dq; a.dk = dk; a.dv = dv; a.delta = delta;
-  a.seg_prefix = seg_prefix; a.seg_len = seg_len; a.use_tr = -1;
-  return done(launch_attn_bwd(a, S(stream)), "opadpo_attn_bwd");
+  a.seg_prefix = seg_prefix; a.seg_len = seg_len;
+  return done(launch_attn_bwd(a, g_flags, S(stream)), "opadpo_attn_bwd");
 }
 
 int opadpo_rmsnorm_fwd(const void* x, int x_f32, const uint16_t* w, uint16_t* y, float* rstd, int rows, int H, float eps, void* stream) {

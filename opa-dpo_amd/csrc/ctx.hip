@@ -246,8 +246,16 @@ struct opadpo_ctx {
   size_t arena_hint[2][16] = {};                  // largest activation arena requested so far, per (no-grad / training pass, responses per row K):
                                                   // CoPO's K = 2 masked pass does not inherit the K = 3 pass's worst case
   std::vector<opadpo_saved*> live;
-  // dispatch
-  int gemm_variant = -1, use_tr = -1;             // -1: process default (opadpo_set_flags)
+  // dispatch: opadpo_ctx_set_flags(gemm_variant, use_tr), parsed once; the use_tr bits below are off for a negative word
+  KernelOverrides kernel;                         // gemm_variant, bits 0, 3 and 8 over the process flags (resolve_flags, per launch)
+  bool streaming_dec_gemm = false;                // bit 5: decode steps of 9..64 sequences keep the 8/16-row streaming GEMMs
+  bool swiglu_bwd_staged = false;                 // bit 6: SwiGLU backward through the LDS-staged epilogue
+  bool top_layer_all_rows = false;                // bit 7: the top layer runs on every row (no compact top layer)
+  bool head_chunk_force = false, head_chunk_off = false;      // bits 9 / 10: chunked head for any size / never
+  bool rope_own_kernel = false;                   // bit 11: rotary embedding in its own kernel, not in the q|k|v epilogue / attention backward
+  bool wgrad_atomic = false;                      // bit 12: the LoRA wgrads keep the fp32-atomic flush
+  bool resid_deferred = false;                    // bit 13: residual adds in the RMSNorm that follows, not in the projections' epilogues
+  bool swiglu_bwd_own_kernel = false;             // bit 14: SwiGLU backward in its own kernel, not in the dgrad's epilogue
   // live profile of the gemm_nt launches (opadpo_ctx_profile)
   bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
@@ -334,14 +342,16 @@ struct Carve {
   template <typename T> T* take(size_t n) { T* r = base ? (T*)(base + off) : nullptr; off += up(n * sizeof(T)); return r; }
 };
 
-GemmNTArgs gemm(const opadpo_ctx* c, const bf16_t* A1, int lda1, const bf16_t* B1, int ldb1, int K1, void* C, int ldc, int out_f32, int M, int N) {
+// the kernel flags of a launch of this context
+KernelFlags ctx_flags(const opadpo_ctx* c) { return resolve_flags(process_flags(), c->kernel); }
+
+GemmNTArgs gemm(const bf16_t* A1, int lda1, const bf16_t* B1, int ldb1, int K1, void* C, int ldc, int out_f32, int M, int N) {
   GemmNTArgs a;
   a.A1 = A1; a.B1 = B1; a.A2 = nullptr; a.B2 = nullptr; a.C = C; a.R = nullptr; a.bias = nullptr;
   a.M = M; a.N = N; a.K1 = K1; a.K2 = 0;
   a.lda1 = lda1; a.ldb1 = ldb1; a.lda2 = 0; a.ldb2 = 0; a.ldc = ldc; a.ldr = 0;
   a.a2_group_n = 0; a.a2_group_stride = 0; a.a1_group_n = 0; a.a1_group_stride = 0;
   a.alpha = 1.f; a.act = 0; a.out_f32 = out_f32; a.r_f32 = 0;
-  a.variant = c->gemm_variant;
   return a;
 }
 inline GemmNTArgs& tail(GemmNTArgs& a, const bf16_t* A2, int lda2, const bf16_t* B2, int ldb2, int K2, int gn = 0, int gs = 0) {
@@ -352,9 +362,10 @@ inline GemmNTArgs& resid(GemmNTArgs& a, const void* R, int ldr, int r_f32) { a.R
 // every gemm_nt launch of the context goes through here: with opadpo_ctx_profile(ctx, 1) each launch is bracketed by HIP events on
 // the launch stream (bench.py's live measurement of the dominant kernel: algorithmic FLOPs / measured duration)
 hipError_t run_gemm(opadpo_ctx* c, const GemmNTArgs& g, hipStream_t st) {
-  const size_t need = gemm_nt_workspace_bytes(g);
+  const KernelFlags f = ctx_flags(c);
+  const size_t need = gemm_nt_workspace_bytes(g, f);
   if (need > c->gemm_ws_bytes && !ws_grow(c, c->gemm_ws, c->gemm_ws_bytes, need + need / 4, st)) return hipErrorOutOfMemory;
-  if (!c->prof) return launch_gemm_nt(g, st, c->gemm_ws, c->gemm_ws_bytes);
+  if (!c->prof) return launch_gemm_nt(g, f, st, c->gemm_ws, c->gemm_ws_bytes);
   hipEvent_t e0, e1;
   hipError_t e;
   if (c->prof_pool.size() >= 2) {
@@ -365,7 +376,7 @@ hipError_t run_gemm(opadpo_ctx* c, const GemmNTArgs& g, hipStream_t st) {
     if ((e = hipEventCreate(&e1)) != hipSuccess) return e;
   }
   if ((e = hipEventRecord(e0, st)) != hipSuccess) return e;
-  e = launch_gemm_nt(g, st, c->gemm_ws, c->gemm_ws_bytes);
+  e = launch_gemm_nt(g, f, st, c->gemm_ws, c->gemm_ws_bytes);
   (void)hipEventRecord(e1, st);
   c->prof_ev.push_back({e0, e1});
   c->prof_flops.push_back(2.0 * (double)g.M * (double)g.N * (double)(g.K1 + g.K2));
@@ -415,22 +426,12 @@ hipError_t ensure_rope(opadpo_ctx* c, int len, hipStream_t st) {
 // ---- one Llama decoder layer over M = S*Lp rows (model.py layer_fwd / mlp_fwd) ------------------------------------------------
 struct LayerBufs { bf16_t *n1, *qkv, *t_qkv, *attn, *t_o, *n2, *t_gu, *gu, *act, *t_d; float *rstd1, *rstd2, *lse, *h; };
 
-// full-sequence passes: residual adds in the o / down projections' epilogues (default) or deferred to the RMSNorm that follows (context flag bit 13;
-// OPADPO_FUSE_RESID=0 makes that the process default - A/B runs)
-static bool fuse_resid(const opadpo_ctx* c) {
-  static const int env = getenv("OPADPO_FUSE_RESID") ? atoi(getenv("OPADPO_FUSE_RESID")) : 1;
-  return c->use_tr >= 0 ? !(c->use_tr & 8192) && env != 0 : env != 0;
-}
-static bool fuse_swiglu_bwd(const opadpo_ctx* c) {
-  static const int env = getenv("OPADPO_FUSE_SWIGLU_BWD") ? atoi(getenv("OPADPO_FUSE_SWIGLU_BWD")) : 1;
-  return c->use_tr >= 0 ? !(c->use_tr & 16384) && env != 0 : env != 0;
-}
 // ydef != nullptr ("deferred residual", the full-sequence passes): the down projection writes its fp32 product to ydef WITHOUT the
 // residual - the RMSNorm that follows adds it (rmsnorm_sum_fwd: x = h + y in the same fp32 arithmetic, so h / x keep their bits).
 // Rounds 2-4 ran the full-sequence passes this way because a residual operand went through the LDS-STAGED epilogue of the 256x256 tile, every load
 // behind the read-back of its row: +0.21-0.28 ms on a 0.6-1.6 ms GEMM (tools/resid_probe.py), while the norm kernel takes the same bytes at
 // 6 TB/s (+0.13 ms).  Round 5: the DIRECT epilogue requests the residual rows one row block ahead of the accumulator read-out (+0.05-0.065 ms per
-// GEMM whatever K, profiles/r05m_resid_probe_k.txt), so the add lives in the projections again (fuse_resid above) and this form is the A/B switch.
+// GEMM whatever K, profiles/r05m_resid_probe_k.txt), so the add lives in the projections again and this form is the A/B switch (context flag bit 13).
 // ydef == nullptr (decode steps: a few rows; fused-residual full-sequence passes): residual in the epilogue, result in xo.
 hipError_t mlp_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const float* h, float* xo, const LayerBufs& b, int M, int stream_hint, hipStream_t st,
                    float* ydef = nullptr, bool norm_done = false) {
@@ -446,27 +447,27 @@ hipError_t mlp_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const fl
   if (!norm_done && (e = launch_rmsnorm_fwd(h, 1, w0.ln2, b.n2, b.rstd2, M, H, d.rms_eps, st)) != hipSuccess) return e;
   bool have_gu = true;
   if (lw) {
-    GemmNTArgs g1_ = gemm(c, b.n2, H, lw + o.a_gu, H, H, b.t_gu, 2 * r, 0, M, 2 * r); g1_.alpha = s; g1_.act |= stream_hint;
+    GemmNTArgs g1_ = gemm(b.n2, H, lw + o.a_gu, H, H, b.t_gu, 2 * r, 0, M, 2 * r); g1_.alpha = s; g1_.act |= stream_hint;
     if ((e = run_gemm(c, g1_, st)) != hipSuccess) return e;
-    GemmNTArgs g2 = gemm(c, b.n2, H, w.wgu, H, H, b.gu, 2 * F, 0, M, 2 * F); tail(g2, b.t_gu, 2 * r, lw + o.b_gu, r, r, F, r); g2.act |= stream_hint;
+    GemmNTArgs g2 = gemm(b.n2, H, w.wgu, H, H, b.gu, 2 * F, 0, M, 2 * F); tail(g2, b.t_gu, 2 * r, lw + o.b_gu, r, r, F, r); g2.act |= stream_hint;
     if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
   } else if (merged && ad.swiglu_pair) {        // SwiGLU fused into the projection's epilogue (rows per 128 = [64 gate | 64 up])
-    GemmNTArgs g2 = gemm(c, b.n2, H, w.wgu, H, H, b.act, F, 0, M, 2 * F); g2.act = OPADPO_ACT_SWIGLU_PAIR | stream_hint;
+    GemmNTArgs g2 = gemm(b.n2, H, w.wgu, H, H, b.act, F, 0, M, 2 * F); g2.act = OPADPO_ACT_SWIGLU_PAIR | stream_hint;
     if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
     have_gu = false;
   } else {
-    GemmNTArgs g2 = gemm(c, b.n2, H, w.wgu, H, H, b.gu, 2 * F, 0, M, 2 * F); g2.act |= stream_hint;
+    GemmNTArgs g2 = gemm(b.n2, H, w.wgu, H, H, b.gu, 2 * F, 0, M, 2 * F); g2.act |= stream_hint;
     if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
   }
   if (have_gu && (e = launch_silu_mul_fwd(b.gu, b.act, M, F, st)) != hipSuccess) return e;
   if (lw) {
-    GemmNTArgs g3 = gemm(c, b.act, F, lw + o.a_d, F, F, b.t_d, r, 0, M, r); g3.alpha = s; g3.act |= stream_hint;
+    GemmNTArgs g3 = gemm(b.act, F, lw + o.a_d, F, F, b.t_d, r, 0, M, r); g3.alpha = s; g3.act |= stream_hint;
     if ((e = run_gemm(c, g3, st)) != hipSuccess) return e;
-    GemmNTArgs g4 = gemm(c, b.act, F, w.wd, F, F, ydef ? ydef : xo, H, 1, M, H); tail(g4, b.t_d, r, lw + o.b_d, r, r); g4.act |= stream_hint;
+    GemmNTArgs g4 = gemm(b.act, F, w.wd, F, F, ydef ? ydef : xo, H, 1, M, H); tail(g4, b.t_d, r, lw + o.b_d, r, r); g4.act |= stream_hint;
     if (!ydef) resid(g4, h, H, 1);
     return run_gemm(c, g4, st);
   }
-  GemmNTArgs g4 = gemm(c, b.act, F, w.wd, F, F, ydef ? ydef : xo, H, 1, M, H); g4.act |= stream_hint;
+  GemmNTArgs g4 = gemm(b.act, F, w.wd, F, F, ydef ? ydef : xo, H, 1, M, H); g4.act |= stream_hint;
   if (!ydef) resid(g4, h, H, 1);
   return run_gemm(c, g4, st);
 }
@@ -497,17 +498,17 @@ hipError_t layer_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const 
   // rotary embedding: on ragged rows (per-row positions at hand) inside the q|k|v projection's epilogue, table-free - one 130-us pass over
   // q and k less per layer and pass; context flag bit 11 keeps the separate in-place kernel (also: padded rows, head_dim 64, small problems
   // that the 256x256 kernel does not take)
-  const bool fuse_rope = rg && hd == 128 && (3 * H) % 256 == 0 && !(c->use_tr >= 0 && (c->use_tr & 2048)) &&
+  const bool fuse_rope = rg && hd == 128 && (3 * H) % 256 == 0 && !c->rope_own_kernel &&
                          (double)M * H * 2 < 4.0e9 && ((M + 255) / 256) * (3 * H / 256) >= 150;
   auto with_rope = [&](GemmNTArgs& g) { if (fuse_rope) { g.rope_pos = rg->row_pos; g.rope_l2theta = log2f(d.rope_theta); g.rope_cols = 2 * H; } };
   if (lw) {
-    GemmNTArgs g1_ = gemm(c, b.n1, H, lw + o.a_qkv, H, H, b.t_qkv, 3 * r, 0, M, 3 * r); g1_.alpha = s;
+    GemmNTArgs g1_ = gemm(b.n1, H, lw + o.a_qkv, H, H, b.t_qkv, 3 * r, 0, M, 3 * r); g1_.alpha = s;
     if ((e = run_gemm(c, g1_, st)) != hipSuccess) return e;
-    GemmNTArgs g2 = gemm(c, b.n1, H, w.wqkv, H, H, b.qkv, 3 * H, 0, M, 3 * H); tail(g2, b.t_qkv, 3 * r, lw + o.b_qkv, r, r, H, r);
+    GemmNTArgs g2 = gemm(b.n1, H, w.wqkv, H, H, b.qkv, 3 * H, 0, M, 3 * H); tail(g2, b.t_qkv, 3 * r, lw + o.b_qkv, r, r, H, r);
     with_rope(g2);
     if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
   } else {
-    GemmNTArgs g2 = gemm(c, b.n1, H, w.wqkv, H, H, b.qkv, 3 * H, 0, M, 3 * H);
+    GemmNTArgs g2 = gemm(b.n1, H, w.wqkv, H, H, b.qkv, 3 * H, 0, M, 3 * H);
     with_rope(g2);
     if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
   }
@@ -523,9 +524,9 @@ hipError_t layer_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const 
   memset(&a, 0, sizeof(a));
   a.q = b.qkv; a.k = b.qkv + H; a.v = b.qkv + 2 * H; a.o = b.attn; a.lse = b.lse; a.key_mask = key_mask;
   a.S = S; a.L = Lp; a.nh = nh; a.hd = hd; a.ld = 3 * H; a.ldo = H; a.causal = 1 | OPADPO_ATTN_SKIP_MASKED_Q; a.scale = 1.0f / sqrtf((float)hd);
-  a.seg_prefix = seg0; a.seg_len = seg1; a.use_tr = c->use_tr;
+  a.seg_prefix = seg0; a.seg_len = seg1;
   if (rg) { a.seq_meta = rg->meta; a.meta_stride = rg->stride; a.n_seg = rg->n_seg; a.rows_total = rg->rows; a.seg_prefix = 0; a.seg_len = 0; }
-  if ((e = launch_attn_fwd(a, st)) != hipSuccess) return e;
+  if ((e = launch_attn_fwd(a, ctx_flags(c), st)) != hipSuccess) return e;
   // top layer with `top`: from here on only the rows the head reads exist (attention needed every row's k, v; nothing reads the
   // o-projection / MLP output of the other rows).  b.t_o / b.h / b.n2 / ... and Y then hold top->n COMPACT rows.
   int Mo = M;
@@ -540,16 +541,16 @@ hipError_t layer_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const 
   // (fp32 residual rows requested one row block ahead of the accumulator read-out, gemm.hip w4_direct_epilogue) and the layer's output
   // x' = h + down(..) the down projection's, written to Y - which the caller makes the next layer's x.  Same fp32 additions on the same
   // operands as rmsnorm_sum_fwd's: h / x keep their bits; the norm passes read 6 instead of 14 bytes per element.
-  const bool fr = fuse_resid(c);
+  const bool fr = !c->resid_deferred;
   float* const o_dst = fr ? b.h : Y;
   if (lw) {
-    GemmNTArgs g3 = gemm(c, attn, H, lw + o.a_o, H, H, b.t_o, r, 0, Mo, r); g3.alpha = s;
+    GemmNTArgs g3 = gemm(attn, H, lw + o.a_o, H, H, b.t_o, r, 0, Mo, r); g3.alpha = s;
     if ((e = run_gemm(c, g3, st)) != hipSuccess) return e;
-    GemmNTArgs g4 = gemm(c, attn, H, w.wo, H, H, o_dst, H, 1, Mo, H); tail(g4, b.t_o, r, lw + o.b_o, r, r);
+    GemmNTArgs g4 = gemm(attn, H, w.wo, H, H, o_dst, H, 1, Mo, H); tail(g4, b.t_o, r, lw + o.b_o, r, r);
     if (fr) resid(g4, xr, H, 1);
     if ((e = run_gemm(c, g4, st)) != hipSuccess) return e;
   } else {
-    GemmNTArgs g4 = gemm(c, attn, H, w.wo, H, H, o_dst, H, 1, Mo, H);
+    GemmNTArgs g4 = gemm(attn, H, w.wo, H, H, o_dst, H, 1, Mo, H);
     if (fr) resid(g4, xr, H, 1);
     if ((e = run_gemm(c, g4, st)) != hipSuccess) return e;
   }
@@ -666,7 +667,16 @@ int opadpo_ctx_set_allocator(opadpo_ctx* c, opadpo_alloc_fn alloc, opadpo_free_f
 
 int opadpo_ctx_set_flags(opadpo_ctx* c, int gemm_variant, int use_tr) {
   if (!c) return (int)hipErrorInvalidValue;
-  c->gemm_variant = gemm_variant; c->use_tr = use_tr;
+  c->kernel = kernel_overrides(gemm_variant, use_tr);
+  const auto bit = [&](int b) { return c->kernel.word && (use_tr >> b & 1); };
+  c->streaming_dec_gemm = bit(5);
+  c->swiglu_bwd_staged = bit(6);
+  c->top_layer_all_rows = bit(7);
+  c->head_chunk_force = bit(9); c->head_chunk_off = bit(10);
+  c->rope_own_kernel = bit(11);
+  c->wgrad_atomic = bit(12);
+  c->resid_deferred = bit(13);
+  c->swiglu_bwd_own_kernel = bit(14);
   return 0;
 }
 
@@ -784,29 +794,29 @@ int opadpo_vision_encode(opadpo_ctx* c, const uint16_t* pixels, int B, uint16_t*
   bf16_t* qkv = cv.take<bf16_t>((size_t)M * 3 * vh); bf16_t* att = cv.take<bf16_t>((size_t)M * vh); bf16_t* f1 = cv.take<bf16_t>((size_t)M * vf);
   int32_t* idx = cv.take<int32_t>((size_t)B * P); bf16_t* tok = cv.take<bf16_t>((size_t)B * P * vh); bf16_t* h0 = cv.take<bf16_t>((size_t)B * P * H);
   CK(launch_im2col(pixels, cols, B, d.image_size, d.patch, kpad, st));
-  { GemmNTArgs g = gemm(c, cols, kpad, c->vis.patch_w, kpad, kpad, patches, vh, 0, B * P, vh); CK(run_gemm(c, g, st)); }
+  { GemmNTArgs g = gemm(cols, kpad, c->vis.patch_w, kpad, kpad, patches, vh, 0, B * P, vh); CK(run_gemm(c, g, st)); }
   CK(launch_vision_embed(patches, c->vis.cls, c->vis.pos, x, B, P, vh, st, 1));
   CK(launch_layernorm_fwd(x, c->vis.pre_ln_w, c->vis.pre_ln_b, x2, M, vh, d.v_eps, st, 1, 1));
   std::swap(x, x2);
   for (const opadpo_vision_layer_weights& w : c->vlayers) {
     CK(launch_layernorm_fwd(x, w.ln1_w, w.ln1_b, n, M, vh, d.v_eps, st, 1, 0));
-    { GemmNTArgs g = gemm(c, n, vh, w.wqkv, vh, vh, qkv, 3 * vh, 0, M, 3 * vh); g.bias = w.bqkv; CK(run_gemm(c, g, st)); }
+    { GemmNTArgs g = gemm(n, vh, w.wqkv, vh, vh, qkv, 3 * vh, 0, M, 3 * vh); g.bias = w.bqkv; CK(run_gemm(c, g, st)); }
     AttnArgs a;
     memset(&a, 0, sizeof(a));
     a.q = qkv; a.k = qkv + vh; a.v = qkv + 2 * vh; a.o = att; a.S = B; a.L = T; a.nh = d.v_heads; a.hd = hd; a.ld = 3 * vh; a.ldo = vh;
-    a.causal = 0; a.scale = 1.0f / sqrtf((float)hd); a.use_tr = c->use_tr;
-    CK(launch_attn_fwd(a, st));
-    { GemmNTArgs g = gemm(c, att, vh, w.wo, vh, vh, x2, vh, 1, M, vh); g.bias = w.bo; resid(g, x, vh, 1); CK(run_gemm(c, g, st)); }
+    a.causal = 0; a.scale = 1.0f / sqrtf((float)hd);
+    CK(launch_attn_fwd(a, ctx_flags(c), st));
+    { GemmNTArgs g = gemm(att, vh, w.wo, vh, vh, x2, vh, 1, M, vh); g.bias = w.bo; resid(g, x, vh, 1); CK(run_gemm(c, g, st)); }
     CK(launch_layernorm_fwd(x2, w.ln2_w, w.ln2_b, n, M, vh, d.v_eps, st, 1, 0));
-    { GemmNTArgs g = gemm(c, n, vh, w.fc1, vh, vh, f1, vf, 0, M, vf); g.bias = w.b1; g.act = OPADPO_ACT_QUICK_GELU; CK(run_gemm(c, g, st)); }
-    { GemmNTArgs g = gemm(c, f1, vf, w.fc2, vf, vf, x, vh, 1, M, vh); g.bias = w.b2; resid(g, x2, vh, 1); CK(run_gemm(c, g, st)); }
+    { GemmNTArgs g = gemm(n, vh, w.fc1, vh, vh, f1, vf, 0, M, vf); g.bias = w.b1; g.act = OPADPO_ACT_QUICK_GELU; CK(run_gemm(c, g, st)); }
+    { GemmNTArgs g = gemm(f1, vf, w.fc2, vf, vf, x, vh, 1, M, vh); g.bias = w.b2; resid(g, x2, vh, 1); CK(run_gemm(c, g, st)); }
   }
   hipLaunchKernelGGL(drop_cls_index_kernel, g1((size_t)B * P), dim3(256), 0, st, idx, B, P);
   CK(hipGetLastError());
   CK(launch_f32_to_bf16(x, n, (size_t)M * vh, st));          // one rounding of hidden_states[-2]: the bf16 operand of the projector
   CK(launch_gather_rows(n, vh, idx, tok, B * P, vh, st));
-  { GemmNTArgs g = gemm(c, tok, vh, c->vis.proj0, vh, vh, h0, H, 0, B * P, H); g.bias = c->vis.proj0_b; g.act = OPADPO_ACT_GELU; CK(run_gemm(c, g, st)); }
-  { GemmNTArgs g = gemm(c, h0, H, c->vis.proj2, H, H, feats, H, 0, B * P, H); g.bias = c->vis.proj2_b; CK(run_gemm(c, g, st)); }
+  { GemmNTArgs g = gemm(tok, vh, c->vis.proj0, vh, vh, h0, H, 0, B * P, H); g.bias = c->vis.proj0_b; g.act = OPADPO_ACT_GELU; CK(run_gemm(c, g, st)); }
+  { GemmNTArgs g = gemm(h0, H, c->vis.proj2, H, H, feats, H, 0, B * P, H); g.bias = c->vis.proj2_b; CK(run_gemm(c, g, st)); }
   return 0;
 }
 
@@ -865,7 +875,7 @@ int opadpo_seq_logprobs_fwd(opadpo_ctx* c, int adapter_id, const int32_t* ids, c
       nu += any;
     }
     sv->ragged = 1; sv->meta_stride = stride; sv->M = row; sv->L = lmax; sv->Rc = cells;
-    sv->Uc = (c->use_tr >= 0 && (c->use_tr & 128)) ? 0 : nu;      // context flag bit 7: top layer on every row
+    sv->Uc = c->top_layer_all_rows ? 0 : nu;
   } else {
     sv->Rc = sv->R;
   }
@@ -877,8 +887,7 @@ int opadpo_seq_logprobs_fwd(opadpo_ctx* c, int adapter_id, const int32_t* ids, c
   // valid rows): chunked 977.2 ms / 217.9 GB, un-chunked 972.9 ms / 220.2 GB per step - below the threshold the one-buffer form is kept (the
   // recomputed lm_head GEMM and 8 short launches cost 0.4 %)
   {
-    const int ut = c->use_tr >= 0 ? c->use_tr : 0;
-    const bool want = (ut & 512) || (!(ut & 1024) && (size_t)std::max(S * K * T, 1) * d.vocab * sizeof(float) >= ((size_t)4 << 30));
+    const bool want = c->head_chunk_force || (!c->head_chunk_off && (size_t)std::max(S * K * T, 1) * d.vocab * sizeof(float) >= ((size_t)4 << 30));
     sv->head_chunk = (want && d.vocab > 4096) ? 4096 : 0;
   }
   sv->bytes = saved_layout(d, sv, nullptr);
@@ -933,7 +942,7 @@ int opadpo_seq_logprobs_fwd(opadpo_ctx* c, int adapter_id, const int32_t* ids, c
   const float* res = sv->x;
   const float* yin = nullptr;
   const TopRows top{sv->urow, sv->Uc, sv->attn_u, sv->hs};                 // hs is free until the head (and |U| <= R rows fit)
-  const bool fr = fuse_resid(c);
+  const bool fr = !c->resid_deferred;
   for (int i = 0; i < d.n_layers; ++i) {
     const LayerBufs lb = slot(d, sv, train ? i : 0);
     float* x = sv->x + (size_t)(train ? i : (i & 1)) * MH;
@@ -961,13 +970,13 @@ int opadpo_seq_logprobs_fwd(opadpo_ctx* c, int adapter_id, const int32_t* ids, c
     const int VC = sv->head_chunk;
     for (int c0 = 0; c0 < d.vocab; c0 += VC) {
       const int n = std::min(VC, d.vocab - c0);
-      GemmNTArgs g = gemm(c, sv->hn, H, c->lm_head + (size_t)c0 * H, H, H, sv->logits, VC, 1, R, n);
+      GemmNTArgs g = gemm(sv->hn, H, c->lm_head + (size_t)c0 * H, H, H, sv->logits, VC, 1, R, n);
       CKS(run_gemm(c, g, st));
       CKS(launch_head_fwd_chunk(sv->logits, VC, sv->labels, 1.0f / temperature, c0, n, c0 == 0, sv->lse_head, sv->h_s, sv->ent, sv->h_zl, R, st));
     }
     CKS(launch_head_fwd_finish(sv->labels, sv->lse_head, sv->h_s, sv->ent, sv->h_zl, head_logp, sv->ent, sv->lse_head, R, st));
   } else {
-    GemmNTArgs g = gemm(c, sv->hn, H, c->lm_head, H, H, sv->logits, d.vocab, 1, R, d.vocab);
+    GemmNTArgs g = gemm(sv->hn, H, c->lm_head, H, H, sv->logits, d.vocab, 1, R, d.vocab);
     CKS(run_gemm(c, g, st));
     CKS(launch_head_fwd(sv->logits, d.vocab, sv->labels, 1.0f / temperature, head_logp, sv->ent, sv->lse_head, R, d.vocab, st));
   }
@@ -1028,16 +1037,16 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
   // fixed order: no fp32 atomics, gradients bit-reproducible run to run): the worst case over the layer's 8 problems as one group, or one
   // by one (compact top layer: two row counts); context flag (use_tr) bit 12 keeps the atomic flush (A/B)
   size_t tn_ws_floats = 1;
-  if (!(c->use_tr >= 0 && (c->use_tr & 4096))) {
+  if (!c->wgrad_atomic) {
     GemmTNArgs shp[8];
     const int n1s[8] = {H, r, 2 * F, 2 * r, H, r, 3 * H, 3 * r}, n2s[8] = {r, F, r, H, r, H, r, H}, qg[8] = {0, 0, F, 0, 0, 0, H, 0};
     for (int rows_case = 0; rows_case < 2; ++rows_case) {
       for (int q = 0; q < 8; ++q) {
         memset(&shp[q], 0, sizeof(GemmTNArgs));
         shp[q].M = (rows_case == 1 && sv->Uc > 0 && q < 6) ? sv->Uc : M;
-        shp[q].N1 = n1s[q]; shp[q].N2 = n2s[q]; shp[q].ldp = n1s[q]; shp[q].ldq = n2s[q] * (qg[q] ? n1s[q] / qg[q] : 1); shp[q].q_group_n1 = qg[q]; shp[q].use_tr = c->use_tr;
+        shp[q].N1 = n1s[q]; shp[q].N2 = n2s[q]; shp[q].ldp = n1s[q]; shp[q].ldq = n2s[q] * (qg[q] ? n1s[q] / qg[q] : 1); shp[q].q_group_n1 = qg[q];
       }
-      tn_ws_floats = std::max(tn_ws_floats, gemm_tn_group_workspace_bytes(shp, 8) / sizeof(float));
+      tn_ws_floats = std::max(tn_ws_floats, gemm_tn_group_workspace_bytes(shp, 8, ctx_flags(c)) / sizeof(float));
     }
   }
   // workspace (persists between the ranged calls of one backward)
@@ -1078,16 +1087,16 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
       // accumulation across the chunks, ONE rounding to bf16 at the end - what the single K = vocab GEMM does inside its accumulators)
       for (int c0 = 0; c0 < V; c0 += VC) {
         const int n = std::min(VC, V - c0);
-        { GemmNTArgs g = gemm(c, sv->hn, H, c->lm_head + (size_t)c0 * H, H, H, sv->logits, VC, 1, R, n); CK(run_gemm(c, g, st)); }
+        { GemmNTArgs g = gemm(sv->hn, H, c->lm_head + (size_t)c0 * H, H, H, sv->logits, VC, 1, R, n); CK(run_gemm(c, g, st)); }
         CK(launch_head_bwd(sv->logits, VC, sv->labels, sv->lse_head, dlogp, dent ? sv->ent : nullptr, dent, 1.0f / sv->temperature, dz, VC, R, n, st, c0));
-        GemmNTArgs g = gemm(c, dz, VC, c->lm_head_t + c0, V, n, d_hn32, H, 1, R, H);
+        GemmNTArgs g = gemm(dz, VC, c->lm_head_t + c0, V, n, d_hn32, H, 1, R, H);
         if (c0 > 0) resid(g, d_hn32, H, 1);
         CK(run_gemm(c, g, st));
       }
       CK(launch_f32_to_bf16(d_hn32, d_hn, (size_t)R * H, st));
     } else {
       CK(launch_head_bwd(sv->logits, V, sv->labels, sv->lse_head, dlogp, dent ? sv->ent : nullptr, dent, 1.0f / sv->temperature, dz, V, R, V, st));
-      GemmNTArgs g = gemm(c, dz, V, c->lm_head_t, V, V, d_hn, H, 0, R, H);
+      GemmNTArgs g = gemm(dz, V, c->lm_head_t, V, V, d_hn, H, 0, R, H);
       CK(run_gemm(c, g, st));
     }
     CK(launch_rmsnorm_bwd(d_hn, sv->hs, 1, c->norm, sv->rstd_f, nullptr, 0, d_hs, nullptr, R, H, st));
@@ -1111,38 +1120,38 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
     const int Mm = top ? sv->Uc : M;
     auto tn = [&](const bf16_t* Pm, int ldp, const bf16_t* Q, int ldq, float* Cg, int ldc, int N1, int N2, int qgn, int qgs, int rows) {
       GemmTNArgs& t = wg[nwg++]; t.P = Pm; t.Q = Q; t.C = Cg; t.M = rows; t.N1 = N1; t.N2 = N2; t.ldp = ldp; t.ldq = ldq; t.ldc = ldc;
-      t.q_group_n1 = qgn; t.q_group_stride = qgs; t.alpha = 1.f; t.splits = 0; t.use_tr = c->use_tr;
+      t.q_group_n1 = qgn; t.q_group_stride = qgs; t.alpha = 1.f; t.splits = 0;
       return hipSuccess;
     };
     // ---- MLP ----
-    { GemmNTArgs g = gemm(c, dXb, H, wt + o.b_d, H, H, dt_r, r, 0, Mm, r); g.alpha = s; CK(run_gemm(c, g, st)); }
+    { GemmNTArgs g = gemm(dXb, H, wt + o.b_d, H, H, dt_r, r, 0, Mm, r); g.alpha = s; CK(run_gemm(c, g, st)); }
     CK(tn(dXb, H, b.t_d, r, gr + o.b_d, r, H, r, 0, 0, Mm));
     CK(tn(dt_r, r, b.act, F, gr + o.a_d, F, r, F, 0, 0, Mm));
-    const bool sb_staged = c->use_tr >= 0 && (c->use_tr & 64);
-    if (F % 256 == 0 && (sb_staged || fuse_swiglu_bwd(c))) {
+    const bool sb_staged = c->swiglu_bwd_staged;
+    if (F % 256 == 0 && (sb_staged || !c->swiglu_bwd_own_kernel)) {
       // SwiGLU backward in the dgrad's epilogue: d_act never reaches HBM.  Default since round 5 in the DIRECT form (gate / up operands requested one
-      // row block ahead of the accumulator read-out, lane-local math, gemm.hip w4_direct_epilogue_swiglu_bwd; context flag bit 14 / OPADPO_FUSE_SWIGLU_BWD=0
-      // keep the two-kernel form).  Flag bit 6 = the LDS-staged form of rounds 3-4 (every operand load's latency exposed: 1016.9 vs 1013.3 ms per step
+      // row block ahead of the accumulator read-out, lane-local math, gemm.hip w4_direct_epilogue_swiglu_bwd; context flag bit 14
+      // keeps the two-kernel form).  Flag bit 6 = the LDS-staged form of rounds 3-4 (every operand load's latency exposed: 1016.9 vs 1013.3 ms per step
       // for the two-kernel form then) - the cross-check of the direct one.
-      GemmNTArgs g = gemm(c, dXb, H, w.wd_t, H, H, d_gu, 2 * F, 0, Mm, F); tail(g, dt_r, r, wt + o.a_d, r, r);
+      GemmNTArgs g = gemm(dXb, H, w.wd_t, H, H, d_gu, 2 * F, 0, Mm, F); tail(g, dt_r, r, wt + o.a_d, r, r);
       g.act = OPADPO_ACT_SWIGLU_BWD; g.R = b.gu; g.ldr = 2 * F; g.r_f32 = 0; g.swiglu_bwd_staged = sb_staged ? 1 : 0;
       CK(run_gemm(c, g, st));
     } else {
-      { GemmNTArgs g = gemm(c, dXb, H, w.wd_t, H, H, d_act, F, 0, Mm, F); tail(g, dt_r, r, wt + o.a_d, r, r); CK(run_gemm(c, g, st)); }
+      { GemmNTArgs g = gemm(dXb, H, w.wd_t, H, H, d_act, F, 0, Mm, F); tail(g, dt_r, r, wt + o.a_d, r, r); CK(run_gemm(c, g, st)); }
       CK(launch_silu_mul_bwd(d_act, b.gu, d_gu, Mm, F, st));
     }
-    { GemmNTArgs g = gemm(c, d_gu, 2 * F, wt + o.b_gu, F, F, dt_2r, 2 * r, 0, Mm, 2 * r); g.alpha = s; g.a1_group_n = r; g.a1_group_stride = F; CK(run_gemm(c, g, st)); }
+    { GemmNTArgs g = gemm(d_gu, 2 * F, wt + o.b_gu, F, F, dt_2r, 2 * r, 0, Mm, 2 * r); g.alpha = s; g.a1_group_n = r; g.a1_group_stride = F; CK(run_gemm(c, g, st)); }
     CK(tn(d_gu, 2 * F, b.t_gu, 2 * r, gr + o.b_gu, r, 2 * F, r, F, r, Mm));
     CK(tn(dt_2r, 2 * r, b.n2, H, gr + o.a_gu, H, 2 * r, H, 0, 0, Mm));
-    { GemmNTArgs g = gemm(c, d_gu, 2 * F, w.wgu_t, 2 * F, 2 * F, d_n, H, 0, Mm, H); tail(g, dt_2r, 2 * r, wt + o.a_gu, 2 * r, 2 * r); CK(run_gemm(c, g, st)); }
+    { GemmNTArgs g = gemm(d_gu, 2 * F, w.wgu_t, 2 * F, 2 * F, d_n, H, 0, Mm, H); tail(g, dt_2r, 2 * r, wt + o.a_gu, 2 * r, 2 * r); CK(run_gemm(c, g, st)); }
     CK(launch_rmsnorm_bwd(d_n, b.h, 1, w.ln2, b.rstd2, dX, 1, d_h, d_hb, Mm, H, st));
     // ---- attention ----
-    { GemmNTArgs g = gemm(c, d_hb, H, wt + o.b_o, H, H, dt_ra, r, 0, Mm, r); g.alpha = s; CK(run_gemm(c, g, st)); }
+    { GemmNTArgs g = gemm(d_hb, H, wt + o.b_o, H, H, dt_ra, r, 0, Mm, r); g.alpha = s; CK(run_gemm(c, g, st)); }
     CK(tn(d_hb, H, b.t_o, r, gr + o.b_o, r, H, r, 0, 0, Mm));
     CK(tn(dt_ra, r, top ? sv->attn_u : b.attn, H, gr + o.a_o, H, r, H, 0, 0, Mm));
     {
       bf16_t* dst = top ? d_n : d_attn;            // d_n is free again: the norm backward above has consumed it
-      GemmNTArgs g = gemm(c, d_hb, H, w.wo_t, H, H, dst, H, 0, Mm, H); tail(g, dt_ra, r, wt + o.a_o, r, r); CK(run_gemm(c, g, st));
+      GemmNTArgs g = gemm(d_hb, H, w.wo_t, H, H, dst, H, 0, Mm, H); tail(g, dt_ra, r, wt + o.a_o, r, r); CK(run_gemm(c, g, st));
       if (top) {                                   // gradient of the attention output: U rows carry one, every other row zero
         CK(hipMemsetAsync(d_attn, 0, MH * sizeof(bf16_t), st));
         CK(launch_scatter_rows(d_n, sv->urow, d_attn, H, Mm, H, st));
@@ -1153,23 +1162,23 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
     a.q = b.qkv; a.k = b.qkv + H; a.v = b.qkv + 2 * H; a.o = b.attn; a.lse = b.lse; a.key_mask = sv->key_mask;
     a.S = S; a.L = Lp; a.nh = nh; a.hd = hd; a.ld = 3 * H; a.ldo = H; a.causal = 1 | OPADPO_ATTN_SKIP_MASKED_Q; a.scale = 1.0f / sqrtf((float)hd);
     a.dout = d_attn; a.dq_acc = nullptr; a.dq = dqkv; a.dk = dqkv + H; a.dv = dqkv + 2 * H; a.delta = delta;
-    a.seg_prefix = sv->seg_prefix; a.seg_len = sv->seg_len; a.use_tr = c->use_tr;
+    a.seg_prefix = sv->seg_prefix; a.seg_len = sv->seg_len;
     if (sv->ragged) { a.seq_meta = sv->meta; a.meta_stride = sv->meta_stride; a.n_seg = sv->K; a.rows_total = M; a.seg_prefix = 0; a.seg_len = 0; }
     // ragged rows: dQ / dK leave the attention backward already rotated back (lane-local in its accumulator layout) - no pass over dq | dk;
     // context flag bit 11 (and padded rows) keep the separate inverse rope kernel
-    const bool fuse_rope_bwd = sv->ragged && !(c->use_tr >= 0 && (c->use_tr & 2048));
+    const bool fuse_rope_bwd = sv->ragged && !c->rope_own_kernel;
     if (fuse_rope_bwd) { a.rope_pos = sv->row_pos; a.rope_l2theta = log2f(d.rope_theta); }
-    CK(launch_attn_bwd(a, st));
+    CK(launch_attn_bwd(a, ctx_flags(c), st));
     if (!fuse_rope_bwd) CK(launch_rope(dqkv, 3 * H, c->cosb, c->sinb, M, Lp, 2 * nh, hd, 1, nullptr, sv->seg_prefix, sv->seg_len, st, sv->ragged ? sv->row_pos : nullptr,
                                        sv->ragged ? log2f(d.rope_theta) : 0.f));
-    { GemmNTArgs g = gemm(c, dqkv, 3 * H, wt + o.b_qkv, H, H, dt_3r, 3 * r, 0, M, 3 * r); g.alpha = s; g.a1_group_n = r; g.a1_group_stride = H; CK(run_gemm(c, g, st)); }
+    { GemmNTArgs g = gemm(dqkv, 3 * H, wt + o.b_qkv, H, H, dt_3r, 3 * r, 0, M, 3 * r); g.alpha = s; g.a1_group_n = r; g.a1_group_stride = H; CK(run_gemm(c, g, st)); }
     CK(tn(dqkv, 3 * H, b.t_qkv, 3 * r, gr + o.b_qkv, r, 3 * H, r, H, r, M));
     CK(tn(dt_3r, 3 * r, b.n1, H, gr + o.a_qkv, H, 3 * r, H, 0, 0, M));
     { int ord = 1;      // what the launches of THIS list actually did (not a synthetic shape list): ordered reduce for every problem, or atomics somewhere
-      CK(launch_gemm_tn_group(wg, nwg, st, tn_ws_floats > 1 ? tn_ws : nullptr, tn_ws_floats > 1 ? tn_ws_floats * sizeof(float) : 0, &ord));
+      CK(launch_gemm_tn_group(wg, nwg, ctx_flags(c), st, tn_ws_floats > 1 ? tn_ws : nullptr, tn_ws_floats > 1 ? tn_ws_floats * sizeof(float) : 0, &ord));
       if (!ord) c->wgrad_det = 0; }
     if (i > 0 || d_feats) {          // layer-0 input is the frozen embedding / image features: no further dgrad in the DPO stage
-      { GemmNTArgs g = gemm(c, dqkv, 3 * H, w.wqkv_t, 3 * H, 3 * H, d_n, H, 0, M, H); tail(g, dt_3r, 3 * r, wt + o.a_qkv, 3 * r, 3 * r); CK(run_gemm(c, g, st)); }
+      { GemmNTArgs g = gemm(dqkv, 3 * H, w.wqkv_t, 3 * H, 3 * H, d_n, H, 0, M, H); tail(g, dt_3r, 3 * r, wt + o.a_qkv, 3 * r, 3 * r); CK(run_gemm(c, g, st)); }
       const float* dres = d_h;
       if (top) {                                   // residual gradient of the block: d_h holds it for the U rows only
         CK(hipMemsetAsync(d_full, 0, MH * sizeof(float), st));
@@ -1196,8 +1205,8 @@ static hipError_t decode_head(opadpo_ctx* c, const float* src_f32, const float* 
   if (n_partials > 0) {
     if ((e = launch_rmsnorm_sum_fwd(src_f32, 1, partials, n_partials, (size_t)D.B * d.hidden, c->norm, D.x2, D.hn, D.rstd, D.B, d.hidden, d.rms_eps, st)) != hipSuccess) return e;
   } else if ((e = launch_rmsnorm_fwd(src_f32, 1, c->norm, D.hn, D.rstd, D.B, d.hidden, d.rms_eps, st)) != hipSuccess) return e;
-  GemmNTArgs g = gemm(c, D.hn, d.hidden, c->lm_head, d.hidden, d.hidden, D.logits, d.vocab, 1, D.B, d.vocab); g.act |= OPADPO_GEMM_STREAM;
-  if (D.use64) e = launch_gemm_nt_dec64(g, 1, 1, st);
+  GemmNTArgs g = gemm(D.hn, d.hidden, c->lm_head, d.hidden, d.hidden, D.logits, d.vocab, 1, D.B, d.vocab); g.act |= OPADPO_GEMM_STREAM;
+  if (D.use64) e = launch_gemm_nt_dec64(g, 1, 1, ctx_flags(c), st);
   else e = run_gemm(c, g, st);
   if (e != hipSuccess) return e;
   if (D.suppress_eos) {
@@ -1227,8 +1236,8 @@ static hipError_t decode_one(opadpo_ctx* c, hipStream_t st) {
     const int F = d.ffn;
     const size_t pstride = (size_t)B * H;
     auto dg = [&](const bf16_t* A, int lda, const bf16_t* W, int K, void* C, int ldc, int N, int mode, int splits) {
-      GemmNTArgs g = gemm(c, A, lda, W, K, K, C, ldc, mode == 1, B, N);
-      return launch_gemm_nt_dec64(g, mode, splits, st);
+      GemmNTArgs g = gemm(A, lda, W, K, K, C, ldc, mode == 1, B, N);
+      return launch_gemm_nt_dec64(g, mode, splits, ctx_flags(c), st);
     };
     for (int i = 0; i < d.n_layers; ++i) {
       const opadpo_layer_weights& w0 = c->layers[i];
@@ -1262,24 +1271,24 @@ static hipError_t decode_one(opadpo_ctx* c, hipStream_t st) {
     const bf16_t* lw = ad.kind == 1 ? ad.work + (size_t)i * o.layer : nullptr;
     if ((e = launch_rmsnorm_fwd(cur, cur_f32, w0.ln1, D.n1, D.rstd, B, H, d.rms_eps, st)) != hipSuccess) return e;
     if (lw) {
-      GemmNTArgs g1_ = gemm(c, D.n1, H, lw + o.a_qkv, H, H, D.t_qkv, 3 * r, 0, B, 3 * r); g1_.alpha = s; g1_.act |= OPADPO_GEMM_STREAM;
+      GemmNTArgs g1_ = gemm(D.n1, H, lw + o.a_qkv, H, H, D.t_qkv, 3 * r, 0, B, 3 * r); g1_.alpha = s; g1_.act |= OPADPO_GEMM_STREAM;
       if ((e = run_gemm(c, g1_, st)) != hipSuccess) return e;
-      GemmNTArgs g2 = gemm(c, D.n1, H, w.wqkv, H, H, D.qkv, 3 * H, 0, B, 3 * H); tail(g2, D.t_qkv, 3 * r, lw + o.b_qkv, r, r, H, r); g2.act |= OPADPO_GEMM_STREAM;
+      GemmNTArgs g2 = gemm(D.n1, H, w.wqkv, H, H, D.qkv, 3 * H, 0, B, 3 * H); tail(g2, D.t_qkv, 3 * r, lw + o.b_qkv, r, r, H, r); g2.act |= OPADPO_GEMM_STREAM;
       if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
     } else {
-      GemmNTArgs g2 = gemm(c, D.n1, H, w.wqkv, H, H, D.qkv, 3 * H, 0, B, 3 * H); g2.act |= OPADPO_GEMM_STREAM;
+      GemmNTArgs g2 = gemm(D.n1, H, w.wqkv, H, H, D.qkv, 3 * H, 0, B, 3 * H); g2.act |= OPADPO_GEMM_STREAM;
       if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
     }
     const size_t per_layer = (size_t)B * nh * D.max_ctx * hd;
     if ((e = launch_attn_decode_fused(D.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * per_layer, D.vc + i * per_layer, D.att, D.key_mask, B, nh, hd, D.pos_d,
                                       D.max_ctx, 1.0f / sqrtf((float)hd), D.ws, D.ws_bytes, st)) != hipSuccess) return e;
     if (lw) {
-      GemmNTArgs g3 = gemm(c, D.att, H, lw + o.a_o, H, H, D.t_o, r, 0, B, r); g3.alpha = s; g3.act |= OPADPO_GEMM_STREAM;
+      GemmNTArgs g3 = gemm(D.att, H, lw + o.a_o, H, H, D.t_o, r, 0, B, r); g3.alpha = s; g3.act |= OPADPO_GEMM_STREAM;
       if ((e = run_gemm(c, g3, st)) != hipSuccess) return e;
-      GemmNTArgs g4 = gemm(c, D.att, H, w.wo, H, H, D.hb, H, 1, B, H); tail(g4, D.t_o, r, lw + o.b_o, r, r); resid(g4, cur, H, cur_f32); g4.act |= OPADPO_GEMM_STREAM;
+      GemmNTArgs g4 = gemm(D.att, H, w.wo, H, H, D.hb, H, 1, B, H); tail(g4, D.t_o, r, lw + o.b_o, r, r); resid(g4, cur, H, cur_f32); g4.act |= OPADPO_GEMM_STREAM;
       if ((e = run_gemm(c, g4, st)) != hipSuccess) return e;
     } else {
-      GemmNTArgs g4 = gemm(c, D.att, H, w.wo, H, H, D.hb, H, 1, B, H); resid(g4, cur, H, cur_f32); g4.act |= OPADPO_GEMM_STREAM;
+      GemmNTArgs g4 = gemm(D.att, H, w.wo, H, H, D.hb, H, 1, B, H); resid(g4, cur, H, cur_f32); g4.act |= OPADPO_GEMM_STREAM;
       if ((e = run_gemm(c, g4, st)) != hipSuccess) return e;
     }
     if ((e = mlp_fwd(c, i, ad, D.hb, nx, b, B, OPADPO_GEMM_STREAM, st)) != hipSuccess) return e;
@@ -1311,11 +1320,10 @@ int opadpo_decode_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const
   D.ws_bytes = attn_decode_workspace_bytes(B, nh, hd, max_ctx);
   // 9..64 sequences without LoRA tails (adapter-free or merged adapter): the decode GEMM for <= 64 tokens (gemm_nt_dec64x_kernel), the o / down
   // projections K-split into fp32 partial tiles that the following RMSNorm adds.  Measured per decode step against the 8/16-row streaming kernels
-  // of the other path: B = 16 4.84 vs 5.15 ms, B = 8 4.12 vs 3.80 ms.  OPADPO_DEC64_MIN (diagnostics): smallest batch taking it.
-  static const int dec64_min = getenv("OPADPO_DEC64_MIN") ? atoi(getenv("OPADPO_DEC64_MIN")) : 9;
-  D.use64 = B >= dec64_min && B <= 64 && ad.kind != 1 && H <= 256 * 8 * 3 && F % 64 == 0 && !(c->use_tr >= 0 && (c->use_tr & 32));
-  D.split_o = D.use64 ? gemm_nt_dec64_splits(H, H, 0) : 1;
-  D.split_d = D.use64 ? gemm_nt_dec64_splits(H, F, 0) : 1;
+  // of the other path: B = 16 4.84 vs 5.15 ms, B = 8 4.12 vs 3.80 ms.  Context flag bit 5 keeps those.
+  D.use64 = B >= 9 && B <= 64 && ad.kind != 1 && H <= 256 * 8 * 3 && F % 64 == 0 && !c->streaming_dec_gemm;
+  D.split_o = D.use64 ? gemm_nt_dec64_splits(H, H, 0, ctx_flags(c)) : 1;
+  D.split_d = D.use64 ? gemm_nt_dec64_splits(H, F, 0, ctx_flags(c)) : 1;
   auto layout = [&](void* base) {
     Carve cv(base);
     const size_t kvn = (size_t)d.n_layers * B * nh * max_ctx * hd;
@@ -1368,7 +1376,7 @@ int opadpo_decode_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const
   const LayerBufs pb = slot(d, &pf, 0);
   float* const Yp = pf.x + 2 * MH;
   const float* yin = nullptr;
-  const bool fr = fuse_resid(c);                    // residual adds in the projections' epilogues: a layer writes its output into the other x slot
+  const bool fr = !c->resid_deferred;              // residual adds in the projections' epilogues: a layer writes its output into the other x slot
   const float* xin = pf.x;
   for (int i = 0; i < d.n_layers; ++i) {
     float* const xo = fr ? pf.x + (size_t)((i + 1) & 1) * MH : Yp;

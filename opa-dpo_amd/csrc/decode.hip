@@ -29,7 +29,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* q, i
                                                                bf16_t* o, const uint8_t* key_mask, int nh, int ctx_arg,
                                                                const int32_t* ctx_ptr, int max_ctx, float scale_log2e, float* ws_part,
                                                                const float* cosb = nullptr, const float* sinb = nullptr,
-                                                               bf16_t* kc_w = nullptr, bf16_t* vc_w = nullptr, int kv_nt = 0) {
+                                                               bf16_t* kc_w = nullptr, bf16_t* vc_w = nullptr) {
   constexpr int LPK = HD / 8;            // lanes per key
   constexpr int KPW = 64 / LPK;          // keys per wave step
   constexpr int NG = NW * KPW;           // lane groups (= keys per block step)
@@ -82,15 +82,11 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* q, i
       kk[u] = make_uint4(0, 0, 0, 0);
       vv[u] = make_uint4(0, 0, 0, 0);
       if (j < s1 && j != pos) {          // slots >= ctx are never read (uninitialised memory may hold NaN bit patterns)
-        // the KV cache is read exactly once per decode step: kv_nt streams it past the L2s (OPADPO_DEC_NT, A/B switch)
+        // the KV cache is read exactly once per decode step: non-temporal loads stream it past the L2s (round 4; same-box B = 64: 9.24 -> 8.93 ms
+        // per step, B = 8 neutral)
         typedef __attribute__((ext_vector_type(4))) unsigned u4n_t;
-        if (kv_nt) {
-          const u4n_t a = __builtin_nontemporal_load((const u4n_t*)(kb + (size_t)j * HD)), c = __builtin_nontemporal_load((const u4n_t*)(vb + (size_t)j * HD));
-          kk[u] = make_uint4(a.x, a.y, a.z, a.w); vv[u] = make_uint4(c.x, c.y, c.z, c.w);
-        } else {
-          kk[u] = *(const uint4*)(kb + (size_t)j * HD);
-          vv[u] = *(const uint4*)(vb + (size_t)j * HD);
-        }
+        const u4n_t a = __builtin_nontemporal_load((const u4n_t*)(kb + (size_t)j * HD)), c = __builtin_nontemporal_load((const u4n_t*)(vb + (size_t)j * HD));
+        kk[u] = make_uint4(a.x, a.y, a.z, a.w); vv[u] = make_uint4(c.x, c.y, c.z, c.w);
       }
     }
     float sc[U];
@@ -624,8 +620,6 @@ __global__ __launch_bounds__(SAMP_T) void sample_kernel_fast(const float* logits
 }  // namespace
 
 static int attn_decode_splits(int B, int nh, int max_ctx) {
-  static const int force = getenv("OPADPO_ATTN_DEC_SPLITS") ? atoi(getenv("OPADPO_ATTN_DEC_SPLITS")) : 0;      // diagnostics
-  if (force > 0) return std::min(force, std::max(1, max_ctx / 256));
   // 257..767 (sequence, head) pairs (9..23 sequences at 32 heads): two key ranges per pair, run as 4-wave workgroups (>= 512 of them) - measured
   // against one 16-wave workgroup per pair: decode step B = 12 4.47 -> 4.27 ms, B = 16 4.58 -> 4.40; from 768 pairs on 4-wave workgroups without a
   // split (B = 24: 5.34 -> 5.12); up to 256 pairs the 16-wave form stays (B = 8: 3.80 against 4.07 with a split)
@@ -643,12 +637,7 @@ static int attn_decode_splits(int B, int nh, int max_ctx) {
   splits = std::min(splits, std::max(1, max_ctx / 256));
   return std::max(1, std::min(splits, 16));
 }
-static bool attn_decode_fat(int B, int nh, int splits) {
-  static const int fat_lim = getenv("OPADPO_ATTN_DEC_FAT") ? atoi(getenv("OPADPO_ATTN_DEC_FAT")) : 512;      // diagnostics: 16-wave workgroups below this many of them
-  return B * nh * splits < fat_lim;
-}
-// the KV cache is read exactly once per decode step: non-temporal loads (round 4; same-box B = 64: 9.24 -> 8.93 ms per step, B = 8 neutral; OPADPO_DEC_NT=0 switches back)
-static int dec_nt() { static const int v = getenv("OPADPO_DEC_NT") ? atoi(getenv("OPADPO_DEC_NT")) : 1; return v; }
+static bool attn_decode_fat(int B, int nh, int splits) { return B * nh * splits < 512; }      // 16-wave workgroups below 512 of them
 size_t attn_decode_workspace_bytes(int B, int nh, int hd, int max_ctx) {
   const int splits = attn_decode_splits(B, nh, max_ctx);
   return splits == 1 ? 0 : (size_t)B * nh * splits * (hd + 2) * 4;
@@ -665,7 +654,7 @@ hipError_t launch_attn_decode_fused(const bf16_t* qkv, int ld, const float* cosb
   const float sl2 = scale * 1.4426950408889634f;
   const bool fat = attn_decode_fat(B, nh, splits);
   const dim3 gr(nh, B, splits);
-#define ADF(HD_, NW_) hipLaunchKernelGGL((attn_decode_kernel<HD_, NW_, true>), gr, dim3(NW_ * 64), 0, st, qkv, ld, kc, vc, o, key_mask, nh, 0, pos_ptr, max_ctx, sl2, part, cosb, sinb, kc, vc, dec_nt())
+#define ADF(HD_, NW_) hipLaunchKernelGGL((attn_decode_kernel<HD_, NW_, true>), gr, dim3(NW_ * 64), 0, st, qkv, ld, kc, vc, o, key_mask, nh, 0, pos_ptr, max_ctx, sl2, part, cosb, sinb, kc, vc)
   if (hd == 128) { if (fat) ADF(128, 16); else ADF(128, 4); }
   else           { if (fat) ADF(64, 16); else ADF(64, 4); }
 #undef ADF
@@ -684,7 +673,7 @@ hipError_t launch_attn_decode(const bf16_t* q, const bf16_t* kc, const bf16_t* v
   const float sl2 = scale * 1.4426950408889634f;
   const bool fat = attn_decode_fat(B, nh, splits);       // few blocks: 16 waves each
   const dim3 gr(nh, B, splits);
-#define AD(HD_, NW_) hipLaunchKernelGGL((attn_decode_kernel<HD_, NW_>), gr, dim3(NW_ * 64), 0, st, q, ldq, kc, vc, o, key_mask, nh, ctx, ctx_ptr, max_ctx, sl2, part, nullptr, nullptr, nullptr, nullptr, dec_nt())
+#define AD(HD_, NW_) hipLaunchKernelGGL((attn_decode_kernel<HD_, NW_>), gr, dim3(NW_ * 64), 0, st, q, ldq, kc, vc, o, key_mask, nh, ctx, ctx_ptr, max_ctx, sl2, part)
   if (hd == 128) { if (fat) AD(128, 16); else AD(128, 4); }
   else           { if (fat) AD(64, 16); else AD(64, 4); }
 #undef AD
@@ -701,10 +690,6 @@ hipError_t launch_rope_kv_append(bf16_t* qkv, int ld, const float* cosb, const f
   return hipGetLastError();
 }
 
-// 1 (default): one-wave tail on the kept tokens after the top-k threshold; 0: the full vocabulary sweeps (identical draws; the exactness test's yardstick)
-static const int env_sample_compact_ = getenv("OPADPO_SAMPLE_COMPACT") ? atoi(getenv("OPADPO_SAMPLE_COMPACT")) : 1;
-static int g_sample_compact = env_sample_compact_;
-void opadpo_set_sample_compact(int on) { g_sample_compact = on < 0 ? env_sample_compact_ : (on ? 1 : 0); }      // -1: the environment decides (as for attn64)
 hipError_t launch_sample(const float* logits, int ldl, int rows, int V, float temperature, int top_k, float top_p,
                          uint64_t seed, uint64_t step, const int32_t* step_ptr, uint8_t* finished, int pad_id, int eos_id,
                          int32_t* out, int32_t* history, hipStream_t st) {
@@ -715,7 +700,9 @@ hipError_t launch_sample(const float* logits, int ldl, int rows, int V, float te
     (void)hipFuncSetAttribute((const void*)sample_kernel_fast, hipFuncAttributeMaxDynamicSharedMemorySize, SAMP_MAXV * 4);
     attr_set = true;
   }
-  const int compact = g_sample_compact;      // process switch (opadpo_set_flags use_tr bit 9 / OPADPO_SAMPLE_COMPACT=0 at load): the same for eager and captured launches
+  // compact (default): one-wave tail on the kept tokens after the top-k threshold; process flag bit 9: the full vocabulary sweeps (identical
+  // draws; the exactness test's yardstick).  A process flag: the same for eager and captured launches
+  const int compact = process_flags().sample_compact ? 1 : 0;
   if (fast)
     hipLaunchKernelGGL(sample_kernel_fast, dim3(rows), dim3(SAMP_T), (size_t)V * 4, st, logits, ldl, V, 1.0f / temperature, top_k, top_p, seed,
                        step, step_ptr, finished, pad_id, eos_id, out, history, compact);

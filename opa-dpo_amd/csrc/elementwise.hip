@@ -4,21 +4,20 @@
 #include "kernels.h"
 
 namespace {
-// 16-byte accesses of tensors that are streamed exactly once by these HBM-bound kernels; `nt` (launch_* : OPADPO_EW_NT) marks them
-// non-temporal so that they do not push the next GEMM's operand panels out of the 4-MiB L2s
+// 16-byte accesses of the tensors these HBM-bound kernels stream
 typedef __attribute__((ext_vector_type(4))) unsigned ew_u4_t;
 typedef __attribute__((ext_vector_type(4))) float ew_f4_t;
-__device__ __forceinline__ uint4 ew_ld16(const void* p, int nt) {
-  const ew_u4_t v = nt ? __builtin_nontemporal_load((const ew_u4_t*)p) : *(const ew_u4_t*)p;
+__device__ __forceinline__ uint4 ew_ld16(const void* p) {
+  const ew_u4_t v = *(const ew_u4_t*)p;
   return make_uint4(v.x, v.y, v.z, v.w);
 }
-__device__ __forceinline__ void ew_st16(void* p, const uint4& v, int nt) {
+__device__ __forceinline__ void ew_st16(void* p, const uint4& v) {
   const ew_u4_t w = {v.x, v.y, v.z, v.w};
-  if (nt) __builtin_nontemporal_store(w, (ew_u4_t*)p); else *(ew_u4_t*)p = w;
+  *(ew_u4_t*)p = w;
 }
-__device__ __forceinline__ void ew_st16f(float* p, float a, float b, float c, float d, int nt) {
+__device__ __forceinline__ void ew_st16f(float* p, float a, float b, float c, float d) {
   const ew_f4_t w = {a, b, c, d};
-  if (nt) __builtin_nontemporal_store(w, (ew_f4_t*)p); else *(ew_f4_t*)p = w;
+  *(ew_f4_t*)p = w;
 }
 
 
@@ -95,7 +94,7 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const void* x, const b
 template <bool XF, bool RF>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* dy, const void* x, const bf16_t* w,
                                                            const float* rstd, const void* dres, float* dx_f32,
-                                                           bf16_t* dx_bf16, int H, int nt) {
+                                                           bf16_t* dx_bf16, int H) {
   __shared__ float red[4];
   const size_t row = blockIdx.x;
   const float r = rstd[row];
@@ -123,10 +122,10 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* dy, cons
       for (int j = 0; j < 8; ++j) o[j] += d[j];
     }
     if (dx_f32) {
-      ew_st16f(dx_f32 + row * H + i, o[0], o[1], o[2], o[3], nt);
-      ew_st16f(dx_f32 + row * H + i + 4, o[4], o[5], o[6], o[7], nt);
+      ew_st16f(dx_f32 + row * H + i, o[0], o[1], o[2], o[3]);
+      ew_st16f(dx_f32 + row * H + i + 4, o[4], o[5], o[6], o[7]);
     }
-    if (dx_bf16) ew_st16(dx_bf16 + row * H + i, pack8(o), nt);
+    if (dx_bf16) ew_st16(dx_bf16 + row * H + i, pack8(o));
   }
 }
 
@@ -322,7 +321,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const bf16_t* dout, const 
 }
 
 // ---- SwiGLU ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void silu_mul_fwd_kernel(const bf16_t* gu, bf16_t* act, size_t rows, int F, int nt) {
+__global__ __launch_bounds__(256) void silu_mul_fwd_kernel(const bf16_t* gu, bf16_t* act, size_t rows, int F) {
   const int per_row = F / 8;
   const size_t total = rows * per_row;
   for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
@@ -333,21 +332,21 @@ __global__ __launch_bounds__(256) void silu_mul_fwd_kernel(const bf16_t* gu, bf1
     unpack8(*(const uint4*)(gu + row * 2 * F + F + i), u);
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = g[j] / (1.0f + __expf(-g[j])) * u[j];
-    ew_st16(act + row * F + i, pack8(o), nt);
+    ew_st16(act + row * F + i, pack8(o));
   }
 }
 
 __global__ __launch_bounds__(256) void silu_mul_bwd_kernel(const bf16_t* dact, const bf16_t* gu, bf16_t* dgu,
-                                                            size_t rows, int F, int nt) {
+                                                            size_t rows, int F) {
   const int per_row = F / 8;
   const size_t total = rows * per_row;
   for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
     const size_t row = idx / per_row;
     const int i = (int)(idx % per_row) * 8;
     float g[8], u[8], d[8], dg[8], du[8];
-    unpack8(ew_ld16(gu + row * 2 * F + i, nt), g);
-    unpack8(ew_ld16(gu + row * 2 * F + F + i, nt), u);
-    unpack8(ew_ld16(dact + row * F + i, nt), d);
+    unpack8(ew_ld16(gu + row * 2 * F + i), g);
+    unpack8(ew_ld16(gu + row * 2 * F + F + i), u);
+    unpack8(ew_ld16(dact + row * F + i), d);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float sg = 1.0f / (1.0f + __expf(-g[j]));
@@ -355,8 +354,8 @@ __global__ __launch_bounds__(256) void silu_mul_bwd_kernel(const bf16_t* dact, c
       du[j] = d[j] * silu;
       dg[j] = d[j] * u[j] * sg * (1.0f + g[j] * (1.0f - sg));
     }
-    ew_st16(dgu + row * 2 * F + i, pack8(dg), nt);
-    ew_st16(dgu + row * 2 * F + F + i, pack8(du), nt);
+    ew_st16(dgu + row * 2 * F + i, pack8(dg));
+    ew_st16(dgu + row * 2 * F + F + i, pack8(du));
   }
 }
 
@@ -559,7 +558,7 @@ __global__ __launch_bounds__(256) void f32_to_bf16_strided_kernel(const float* i
 // deterministic, no atomics - and costs no launch).  One block per row, row held in registers between the two passes.
 template <bool RF>
 __global__ __launch_bounds__(256) void rmsnorm_sum_fwd_kernel(const void* resid, const float* partials, int n_partials, size_t partial_stride,
-                                                               const bf16_t* w, float* x_out, bf16_t* y, float* rstd, int H, float eps, int nt) {
+                                                               const bf16_t* w, float* x_out, bf16_t* y, float* rstd, int H, float eps) {
   __shared__ float red[4];
   const size_t row = blockIdx.x;
   float f[3][8], g[3][8];
@@ -576,8 +575,8 @@ __global__ __launch_bounds__(256) void rmsnorm_sum_fwd_kernel(const void* resid,
         f[it][0] += a.x; f[it][1] += a.y; f[it][2] += a.z; f[it][3] += a.w;
         f[it][4] += b.x; f[it][5] += b.y; f[it][6] += b.z; f[it][7] += b.w;
       }
-      ew_st16f(x_out + row * H + i, f[it][0], f[it][1], f[it][2], f[it][3], nt);
-      ew_st16f(x_out + row * H + i + 4, f[it][4], f[it][5], f[it][6], f[it][7], nt);
+      ew_st16f(x_out + row * H + i, f[it][0], f[it][1], f[it][2], f[it][3]);
+      ew_st16f(x_out + row * H + i + 4, f[it][4], f[it][5], f[it][6], f[it][7]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) ss += f[it][j] * f[it][j];
     }
@@ -592,7 +591,7 @@ __global__ __launch_bounds__(256) void rmsnorm_sum_fwd_kernel(const void* resid,
     if (i < H) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) f[it][j] = f[it][j] * r * g[it][j];
-      ew_st16(y + row * H + i, pack8(f[it]), nt);
+      ew_st16(y + row * H + i, pack8(f[it]));
     }
   }
 }
@@ -613,23 +612,19 @@ hipError_t launch_rmsnorm_fwd(const void* x, int x_f32, const bf16_t* w, bf16_t*
   else hipLaunchKernelGGL(rmsnorm_fwd_kernel<false>, dim3(rows), dim3(256), 0, st, x, w, y, rstd, H, eps);
   return hipGetLastError();
 }
-// OPADPO_EW_NT=1: non-temporal stores (and streamed-once loads) in the four HBM-bound passes between the GEMMs (A/B switch, see ew_st16)
-static int ew_nt() { static const int v = getenv("OPADPO_EW_NT") ? atoi(getenv("OPADPO_EW_NT")) : 0; return v; }
 hipError_t launch_rmsnorm_sum_fwd(const void* resid, int resid_f32, const float* partials, int n_partials, size_t partial_stride, const bf16_t* w,
                                   float* x_out, bf16_t* y, float* rstd, int rows, int H, float eps, hipStream_t st) {
   if (rows <= 0) return hipSuccess;
   if (H % 8 || H > 256 * 8 * 3 || n_partials < 0 || (n_partials > 0 && !partials) || !x_out) return hipErrorInvalidValue;
-  const int nt = rows >= 4096 ? ew_nt() : 0;       // decode-sized calls keep their rows in cache
-  if (resid_f32) hipLaunchKernelGGL(rmsnorm_sum_fwd_kernel<true>, dim3(rows), dim3(256), 0, st, resid, partials, n_partials, partial_stride, w, x_out, y, rstd, H, eps, nt);
-  else hipLaunchKernelGGL(rmsnorm_sum_fwd_kernel<false>, dim3(rows), dim3(256), 0, st, resid, partials, n_partials, partial_stride, w, x_out, y, rstd, H, eps, nt);
+  if (resid_f32) hipLaunchKernelGGL(rmsnorm_sum_fwd_kernel<true>, dim3(rows), dim3(256), 0, st, resid, partials, n_partials, partial_stride, w, x_out, y, rstd, H, eps);
+  else hipLaunchKernelGGL(rmsnorm_sum_fwd_kernel<false>, dim3(rows), dim3(256), 0, st, resid, partials, n_partials, partial_stride, w, x_out, y, rstd, H, eps);
   return hipGetLastError();
 }
 hipError_t launch_rmsnorm_bwd(const bf16_t* dy, const void* x, int x_f32, const bf16_t* w, const float* rstd, const void* dres,
                               int dres_f32, float* dx_f32, bf16_t* dx_bf16, int rows, int H, hipStream_t st) {
   if (rows <= 0) return hipSuccess;
   if (H % 8) return hipErrorInvalidValue;
-  const int nt = rows >= 4096 ? ew_nt() : 0;
-#define RB(XF, RF) hipLaunchKernelGGL((rmsnorm_bwd_kernel<XF, RF>), dim3(rows), dim3(256), 0, st, dy, x, w, rstd, dres, dx_f32, dx_bf16, H, nt)
+#define RB(XF, RF) hipLaunchKernelGGL((rmsnorm_bwd_kernel<XF, RF>), dim3(rows), dim3(256), 0, st, dy, x, w, rstd, dres, dx_f32, dx_bf16, H)
   if (x_f32 && dres_f32) RB(true, true);
   else if (x_f32) RB(true, false);
   else if (dres_f32) RB(false, true);
@@ -676,13 +671,13 @@ hipError_t launch_rope(bf16_t* qk, int ld, const float* cosb, const float* sinb,
 hipError_t launch_silu_mul_fwd(const bf16_t* gu, bf16_t* act, int rows, int F, hipStream_t st) {
   if (rows <= 0) return hipSuccess;
   if (F % 8) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(silu_mul_fwd_kernel, dim3(ew_grid((size_t)rows * (F / 8))), dim3(256), 0, st, gu, act, (size_t)rows, F, rows >= 4096 ? ew_nt() : 0);
+  hipLaunchKernelGGL(silu_mul_fwd_kernel, dim3(ew_grid((size_t)rows * (F / 8))), dim3(256), 0, st, gu, act, (size_t)rows, F);
   return hipGetLastError();
 }
 hipError_t launch_silu_mul_bwd(const bf16_t* dact, const bf16_t* gu, bf16_t* dgu, int rows, int F, hipStream_t st) {
   if (rows <= 0) return hipSuccess;
   if (F % 8) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(silu_mul_bwd_kernel, dim3(ew_grid((size_t)rows * (F / 8))), dim3(256), 0, st, dact, gu, dgu, (size_t)rows, F, rows >= 4096 ? ew_nt() : 0);
+  hipLaunchKernelGGL(silu_mul_bwd_kernel, dim3(ew_grid((size_t)rows * (F / 8))), dim3(256), 0, st, dact, gu, dgu, (size_t)rows, F);
   return hipGetLastError();
 }
 hipError_t launch_embed_splice(const int32_t* ids, const uint8_t* text_mask, const bf16_t* embed, const bf16_t* feats,

@@ -1911,17 +1911,6 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmTNArgs p) {
       }
 }
 
-
-// ---- gemm_tn, wide tiles ------------------------------------------------------------------------------------------
-// The LoRA wgrads are tall-skinny reductions over M: dB = dY^T t has N2 = r = 256, dA = dT^T x has N1 = r, 2r or 3r.  With the
-// 128x128 tile the BIG operand (dY, resp. x) is fetched once per 128-wide slice of the small one — twice for dB, up to six
-// times for dA(q|k|v) — and the kernel runs at HBM speed on re-reads (dB(gate|up): 2 x 1.43 GB in 0.71 ms).  Here the tile
-// spans 256 of the small dimension (BN1 x BN2 = 128 x 256 for dB, 256 x 128 for dA; 4 waves of 64x128 / 128x64), rows past the
-// block's M-slice come back as zeros from a per-block buffer descriptor (no predicates, scalar row offsets), and each
-// transposed LDS fragment feeds 4 or 8 MFMAs instead of 4.
-// MEASURED (M = 32362, one decoder layer's 8 wgrads): 2.60 ms vs 2.37 ms with the 128x128 kernel — the re-reads hit the L2 /
-// Infinity Cache (the slices of one row block run concurrently), and at ~250 VGPRs the wide kernel hides less latency:
-// dA(down) 0.32 vs 0.38 ms, but dB(*) 0.18-0.78 vs 0.13-0.71 ms.  Kept behind set_flags(use_tr bit 2), off by default.
 }  // namespace
 
 namespace {
@@ -2263,39 +2252,6 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_kernel(GemmTNGroup G, int 
 }
 }  // namespace
 
-// ---- process flags (opadpo_set_flags): one value, read by the dispatch of gemm_nt, gemm_tn and attention ------------------------------
-struct GemmFlags {
-  int variant = 10;             // gemm_variant: 10 (default) auto; 4: 128x128 kernel; 17: 8-wave 256x256 kernel (p8); 31: 4-wave 256x256 kernel (w4) forced; 15: M <= 64 streaming
-  bool use_tr = true;           // use_tr bit 0: transposed LDS reads
-  bool tn_w4 = true;            // bit 3 CLEARS it: 256x256 gemm_tn_w4_kernel (default) vs the 128x128 kernel
-  bool skinny8 = true;          // bit 4 CLEARS it: M <= 16 decode GEMMs: whole-cache-line form of the streaming kernel
-  int dec64_variant = 0;        // bits 5-6: 0 / 3 the whole-line streaming kernel (dec64x), 1 / 2 the LDS-ring kernel
-  int dec64x_nw = 0;            // bits 7-8: rows per workgroup of the dec64x kernel (0 = by shape, 1 / 2 / 3 = 48 / 64 / 128; tests)
-  bool w4s_few = false;         // bit 10 (tests): 8 workgroups walk the tile list, so small problems exercise long walks
-  bool w4_nodeep = false;       // bit 11 (tests, A/B): the products of >= 128 K-tiles keep the default K-loop text (round 6: they run the DEEP text)
-  bool w4_chunk_deal = false;   // bit 12 (tests, A/B): every XCD walks a contiguous chunk of the tile order (rounds 1-5) instead of the block-cyclic deal
-};
-static GemmFlags gemm_flags(int gemm_variant, int use_tr) {
-  GemmFlags f;
-  f.variant = gemm_variant;
-  f.use_tr = (use_tr & 1) != 0;
-  f.tn_w4 = (use_tr & 8) == 0;
-  f.skinny8 = (use_tr & 16) == 0;
-  f.dec64_variant = (use_tr >> 5) & 3;
-  f.dec64x_nw = (use_tr >> 7) & 3;
-  f.w4s_few = (use_tr & 1024) != 0;
-  f.w4_nodeep = (use_tr & 2048) != 0;
-  f.w4_chunk_deal = (use_tr & 4096) != 0;
-  return f;
-}
-static GemmFlags g_flags;
-void opadpo_set_flags_impl(int use_glds, int use_tr) {
-  g_flags = gemm_flags(use_glds, use_tr);
-  opadpo_set_attn_dma((use_tr & 2) != 0);
-  opadpo_set_sample_compact((use_tr & 512) ? 0 : -1);      // bit 9 forces the diagnostic sampler; otherwise OPADPO_SAMPLE_COMPACT decides
-}
-bool opadpo_flag_tr() { return g_flags.use_tr; }
-
 // piece order of the 256x256 kernels: the B pieces of a K-tile first for <= 16 column tiles (o / down / the dgrads) and - under the block-cyclic deal, where the A panels
 // of a round are shared chip-wide - for the shallow products of up to 64 column tiles as well (q|k|v: +0.8-1.8 % at 7B, +0.9 % at 13B; the widest shapes lose 5-7 % with it:
 // profiles/r06zz_ab_order_cyclic.txt, r06zz_ab_order_other_shapes.txt); otherwise the A pieces first.  A placement choice: the results do not depend on it.
@@ -2333,7 +2289,7 @@ static bool gemm_nt_kfold_ok(const GemmNTArgs& a, int variant) {
 static size_t gemm_nt_fold_bytes(const GemmNTArgs& a, int variant) {
   return a.M > 0 && gemm_nt_kfold_ok(a, variant) ? (size_t)a.M * 512 * sizeof(float) : 0;
 }
-size_t gemm_nt_workspace_bytes(const GemmNTArgs& a) { return gemm_nt_fold_bytes(a, a.variant >= 0 ? a.variant : g_flags.variant); }
+size_t gemm_nt_workspace_bytes(const GemmNTArgs& a, const KernelFlags& f) { return gemm_nt_fold_bytes(a, f.variant); }
 
 // grid + flush geometry of one launch of gemm_tn_w4_kernel over the group's tile list
 static void tn_w4_geometry(GemmTNGroup& G, int& n_runs, int& smax) {
@@ -2363,12 +2319,11 @@ static hipError_t tn_w4_launch(GemmTNGroup& G, hipStream_t st, void* ws, size_t 
   if (det) hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3(G.tile_end[G.n - 1], 4), dim3(256), 0, st, G, n_runs);      // 4 x 4096 float4 = one 256x256 tile
   return hipGetLastError();
 }
-static bool tn_w4_ok(const GemmTNArgs& a, int M0) {
+static bool tn_w4_ok(const GemmTNArgs& a, int M0, const KernelFlags& f) {
   const bool off32 = (double)a.M * a.ldp * 2 < 4.0e9 && (double)a.M * a.ldq * 2 < 4.0e9;
-  return a.M == M0 && a.M > 0 && a.splits <= 0 && off32 && a.N1 % 256 == 0 && a.N2 % 256 == 0 && (a.q_group_n1 <= 0 || a.q_group_n1 % 256 == 0) &&
-         (a.use_tr < 0 ? g_flags.tn_w4 : (a.use_tr & 8) == 0);
+  return a.M == M0 && a.M > 0 && a.splits <= 0 && off32 && a.N1 % 256 == 0 && a.N2 % 256 == 0 && (a.q_group_n1 <= 0 || a.q_group_n1 % 256 == 0) && f.tn_w4;
 }
-size_t gemm_tn_group_workspace_bytes(const GemmTNArgs* list, int n) {
+size_t gemm_tn_group_workspace_bytes(const GemmTNArgs* list, int n, const KernelFlags& f) {
   // worst case over the ways launch_gemm_tn_group may run the list: one grouped launch, or one launch per problem (problems of different M)
   size_t need = 0;
   auto one = [&](const GemmTNArgs* l, int k) {
@@ -2383,21 +2338,18 @@ size_t gemm_tn_group_workspace_bytes(const GemmTNArgs* list, int n) {
   if (n <= 0 || n > 8) return 0;
   // 0 unless EVERY problem of the list runs on the 256x256 kernel (grouped or alone): a mixed list would send the others to the 128x128
   // kernel's fp32 atomics behind an API that promises a bit-reproducible result
-  for (int i = 0; i < n; ++i) if (list[i].M > 0 && !tn_w4_ok(list[i], list[i].M)) return 0;
+  for (int i = 0; i < n; ++i) if (list[i].M > 0 && !tn_w4_ok(list[i], list[i].M, f)) return 0;
   bool group = true;
-  for (int i = 0; i < n; ++i) group = group && tn_w4_ok(list[i], list[0].M);
+  for (int i = 0; i < n; ++i) group = group && tn_w4_ok(list[i], list[0].M, f);
   if (group) one(list, n);
-  for (int i = 0; i < n; ++i) if (tn_w4_ok(list[i], list[i].M)) one(list + i, 1);
+  for (int i = 0; i < n; ++i) if (tn_w4_ok(list[i], list[i].M, f)) one(list + i, 1);
   return need;
 }
 
-hipError_t launch_gemm_tn(const GemmTNArgs& a, hipStream_t st) {
+hipError_t launch_gemm_tn(const GemmTNArgs& a, const KernelFlags& f, hipStream_t st) {
   if (a.M <= 0) return hipSuccess;
   if (a.N1 % 128 || a.N2 % 128) return hipErrorInvalidValue;
-  const bool use_tr = a.use_tr >= 0 ? (a.use_tr & 1) != 0 : g_flags.use_tr;      // per-call override (opadpo_ctx_set_flags)
-  const bool tn_w4 = a.use_tr >= 0 ? (a.use_tr & 8) == 0 : g_flags.tn_w4;
-  const bool off32 = (double)a.M * a.ldp * 2 < 4.0e9 && (double)a.M * a.ldq * 2 < 4.0e9;
-  if (tn_w4 && a.splits <= 0 && off32 && a.N1 % 256 == 0 && a.N2 % 256 == 0 && (a.q_group_n1 <= 0 || a.q_group_n1 % 256 == 0)) {
+  if (tn_w4_ok(a, a.M, f)) {
     GemmTNGroup G;
     G.g[0] = a; G.n = 1;
     G.tile_end[0] = (a.N1 / 256) * (a.N2 / 256);
@@ -2412,7 +2364,7 @@ hipError_t launch_gemm_tn(const GemmTNArgs& a, hipStream_t st) {
     if (splits < 1) splits = 1;
   }
   const dim3 grid(tiles, splits);
-  if (use_tr) hipLaunchKernelGGL(gemm_tn_kernel<true>, grid, dim3(256), 0, st, a);
+  if (f.use_tr) hipLaunchKernelGGL(gemm_tn_kernel<true>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(gemm_tn_kernel<false>, grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
@@ -2709,7 +2661,7 @@ struct GemmPlan {
 
 // the 4-wave 256x256 kernel over `tiles` output tiles.  Streaming form (gemm_nt_w4s_kernel, round 5) for the plain products whenever every workgroup gets at
 // least two tiles: one workgroup per CU walks the tile list and keeps its K-tile pipeline full across output tiles; variant 31: one tile per workgroup (cross-check).
-void plan_w4(GemmPlan& p, const GemmNTArgs& a, int tiles, const GemmFlags& f, int variant, int cus) {
+void plan_w4(GemmPlan& p, const GemmNTArgs& a, int tiles, const KernelFlags& f, int variant, int cus) {
   const int ob = w4_b_first(a), nt = (a.K1 + a.K2) / P_BK, wgs = f.w4s_few ? 8 : cus;
   const bool walk = variant != 31 && a.K1 / P_BK >= 3 && tiles >= 2 * wgs;
   const bool plain = !a.bias && !a.rope_cos && !a.rope_pos && a.b1_fold_n == 0 && a.act == 0 && (!a.R || w4_direct_resid_ok(a));
@@ -2725,11 +2677,11 @@ void plan_w4(GemmPlan& p, const GemmNTArgs& a, int tiles, const GemmFlags& f, in
   else p.add(K_W4 + (!f.w4_nodeep && nt >= 128 ? 4 : 0) + ob, dim3(tiles), a);      // the deep-K products (down, the dgrads): the DEEP text
 }
 
-hipError_t plan_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, const GemmFlags& f, GemmPlan& p);
+hipError_t plan_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, const KernelFlags& f, GemmPlan& p);
 
-hipError_t plan_gemm_nt(const GemmNTArgs& a_in, const GemmFlags& f, int cus, void* ws, GemmPlan& p) {
+hipError_t plan_gemm_nt(const GemmNTArgs& a_in, const KernelFlags& f, int cus, void* ws, GemmPlan& p) {
   if (a_in.M <= 0) return hipSuccess;
-  const int variant = a_in.variant >= 0 ? a_in.variant : f.variant;      // per-call override (opadpo_ctx_set_flags)
+  const int variant = f.variant;
   if (gemm_nt_kfold_ok(a_in, variant)) {      // the folded launch of the 256x256 kernel, then the pass that adds the halves
     GemmNTArgs fo = a_in;
     fo.N = 512; fo.K1 = a_in.K1 / 2; fo.a1_group_n = 256; fo.a1_group_stride = a_in.K1 / 2; fo.b1_fold_n = 256; fo.b1_fold_koff = a_in.K1 / 2;
@@ -2886,7 +2838,7 @@ hipError_t plan_gemm_nt(const GemmNTArgs& a_in, const GemmFlags& f, int cus, voi
   return hipSuccess;
 }
 
-int dec64_splits(int N, int K, int splits, const GemmFlags& f) {
+int dec64_splits(int N, int K, int splits, const KernelFlags& f) {
   const int nt = K / D_BK, tiles = N / D_BN;
   if (splits <= 0) {
     // workgroup target of the K-split, counted in 64-row tiles: 256 = four K-slices for the 7B o / down projections (the dec64x kernel then
@@ -2900,7 +2852,7 @@ int dec64_splits(int N, int K, int splits, const GemmFlags& f) {
   return splits > nt ? nt : splits;
 }
 
-hipError_t plan_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, const GemmFlags& f, GemmPlan& p) {
+hipError_t plan_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, const KernelFlags& f, GemmPlan& p) {
   if (a.M <= 0) return hipSuccess;
   if (a.M > 64 || a.N % 128 || a.K1 % D_BK || a.K1 <= 0 || a.K2 != 0 || a.lda1 % 8 || a.ldb1 % 8 || mode < 0 || mode > 2) return hipErrorInvalidValue;
   if ((double)a.M * a.lda1 * 2 >= 4.0e9 || (double)a.N * a.ldb1 * 2 >= 4.0e9) return hipErrorInvalidValue;          // 32-bit buffer offsets
@@ -2938,10 +2890,7 @@ hipError_t launch_plan(const GemmPlan& p, hipStream_t st) {
   for (int i = 0; i < p.n; ++i) {
     const GemmLaunch& l = p.l[i];
     const GemmKernel& k = g_kernels[l.kernel];
-    if (!g_kernel_attr[l.kernel]) {
-      if (k.lds > 0) (void)hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
-      g_kernel_attr[l.kernel] = true;
-    }
+    set_lds_once(g_kernel_attr[l.kernel], k.fn, k.lds);
     GemmNTArgs args = l.args;
     int n_tiles = l.n_tiles, ldc = args.ldc, M = args.M, N = args.N;
     const float* ws = l.fold_ws;
@@ -2964,22 +2913,22 @@ int device_cus() {
 }
 }  // namespace
 
-hipError_t launch_gemm_nt(const GemmNTArgs& a, hipStream_t st, void* ws, size_t ws_bytes) {
+hipError_t launch_gemm_nt(const GemmNTArgs& a, const KernelFlags& f, hipStream_t st, void* ws, size_t ws_bytes) {
   GemmPlan p;
-  const hipError_t e = plan_gemm_nt(a, g_flags, device_cus(), ws, p);
+  const hipError_t e = plan_gemm_nt(a, f, device_cus(), ws, p);
   if (e != hipSuccess) return e;
   if (p.ws_bytes > (ws ? ws_bytes : 0)) return hipErrorInvalidValue;      // the caller sizes the workspace with gemm_nt_workspace_bytes
   return launch_plan(p, st);
 }
-hipError_t launch_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, hipStream_t st) {
+hipError_t launch_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, const KernelFlags& f, hipStream_t st) {
   GemmPlan p;
-  const hipError_t e = plan_gemm_nt_dec64(a, mode, splits, g_flags, p);
+  const hipError_t e = plan_gemm_nt_dec64(a, mode, splits, f, p);
   return e != hipSuccess ? e : launch_plan(p, st);
 }
-int gemm_nt_dec64_splits(int N, int K, int splits) { return dec64_splits(N, K, splits, g_flags); }
-hipError_t gemm_nt_plan_text(const GemmNTArgs& a, int gemm_variant, int use_tr, int cus, char* out, size_t out_len) {
+int gemm_nt_dec64_splits(int N, int K, int splits, const KernelFlags& f) { return dec64_splits(N, K, splits, f); }
+hipError_t gemm_nt_plan_text(const GemmNTArgs& a, const KernelFlags& f, int cus, char* out, size_t out_len) {
   GemmPlan p;
-  const hipError_t e = plan_gemm_nt(a, gemm_flags(gemm_variant, use_tr), cus, nullptr, p);
+  const hipError_t e = plan_gemm_nt(a, f, cus, nullptr, p);
   if (e != hipSuccess) return e;
   size_t used = 0;
   if (out_len) out[0] = 0;
@@ -2992,16 +2941,16 @@ hipError_t gemm_nt_plan_text(const GemmNTArgs& a, int gemm_variant, int use_tr, 
   return hipSuccess;
 }
 
-hipError_t launch_gemm_tn_group(const GemmTNArgs* list, int n, hipStream_t st, void* workspace, size_t workspace_bytes, int* all_ordered) {
+hipError_t launch_gemm_tn_group(const GemmTNArgs* list, int n, const KernelFlags& f, hipStream_t st, void* workspace, size_t workspace_bytes, int* all_ordered) {
   // *all_ordered (optional) = 1 when EVERY problem of this call left through the ordered reduce (bit-reproducible), 0 when any took fp32 atomics
   if (all_ordered) *all_ordered = 1;
   if (n <= 0) return hipSuccess;
   bool ok = n <= 8;
-  for (int i = 0; i < n && ok; ++i) ok = tn_w4_ok(list[i], list[0].M);
+  for (int i = 0; i < n && ok; ++i) ok = tn_w4_ok(list[i], list[0].M, f);
   if (!ok) {                                   // not groupable (e.g. the compact top layer: two row counts): one launch per problem
     for (int i = 0; i < n; ++i) {
       hipError_t e;
-      if (list[i].M > 0 && tn_w4_ok(list[i], list[i].M)) {
+      if (list[i].M > 0 && tn_w4_ok(list[i], list[i].M, f)) {
         GemmTNGroup G;
         G.g[0] = list[i]; G.n = 1;
         G.tile_end[0] = (list[i].N1 / 256) * (list[i].N2 / 256);
@@ -3009,7 +2958,7 @@ hipError_t launch_gemm_tn_group(const GemmTNArgs* list, int n, hipStream_t st, v
         e = tn_w4_launch(G, st, workspace, workspace_bytes, &ord);      // launches of one stream run in order: the workspace is free again
         if (all_ordered && !ord) *all_ordered = 0;
       } else {
-        e = launch_gemm_tn(list[i], st);
+        e = launch_gemm_tn(list[i], f, st);
         if (all_ordered && list[i].M > 0) *all_ordered = 0;
       }
       if (e != hipSuccess) return e;

@@ -31,7 +31,7 @@ struct GemmNTArgs {
   const int32_t* rope_pos = nullptr;
   float rope_l2theta = 0.f;
   int group_m = 8;                      // row tiles per group of the grouped tile order (256x256 4-wave kernel)
-  int variant = -1;                     // kernel-variant override of this call (opadpo_ctx_set_flags); -1 = process default (opadpo_set_flags)
+  int pad0 = 0;                         // unused: keeps the kernel-argument layout (these structs are kernel arguments, their offsets are in the kernels' code)
   int tile0 = 0;
   // quarter-tile tail launch of the 128x128 kernel (set by launch_gemm_nt only): block b computes quarter (b & 3) of the 256x256 tile
   // tile0 + (b >> 2) of the 4-wave kernel's grouped tile order - the full K range, so every output element keeps the summation order
@@ -54,7 +54,7 @@ struct GemmTNArgs {
   int q_group_n1, q_group_stride;       // Q column offset = (n1_0 / q_group_n1) * q_group_stride
   float alpha;
   int splits;                           // <=0: auto
-  int use_tr = -1;                      // per-call override of the transposed-LDS-read switch; -1 = process default
+  int pad0 = 0;                         // unused: keeps the kernel-argument layout (GemmTNGroup holds 8 of these)
 };
 
 struct AttnArgs {
@@ -72,7 +72,7 @@ struct AttnArgs {
   float* dq_acc;                                        // optional fp32 copy of dQ [S*L, nh*hd] (nullable)
   bf16_t* dq; bf16_t* dk; bf16_t* dv;                   // ld addressing (same as q / k / v)
   float* delta;                                         // [S, nh, L] scratch
-  int use_tr;                                           // per-call override of the transposed-LDS-read switch; < 0 = process default
+  int pad0;                                             // unused: keeps the kernel-argument layout
   // RAGGED rows (nullable; opadpo_ctx only): the padding rows are removed from the flat [rows, ld] buffers.  seq_meta[s * meta_stride
   // + 0] = first row of sequence s, [1 .. 1 + n_seg] = boundaries relative to it: b_0 = end of the prefix (= start of response 0),
   // b_a = start of response a, b_nseg = length of the sequence.  L = longest sequence (grid), lse / delta are [nh, rows_total],
@@ -97,34 +97,69 @@ struct GemmTNGroup {
   int smax = 0;
 };
 
-void opadpo_set_flags_impl(int use_glds, int use_tr);
+// ---- kernel flags: every kernel choice is a function of the arguments and one KernelFlags value ------------------------------------------
+// the process value is opadpo_set_flags(gemm_variant, use_tr) decoded by kernel_flags; an opadpo_ctx overrides a few fields (resolve_flags)
+struct KernelFlags {
+  int variant = 10;             // gemm_variant: 10 (default) auto; 4: 128x128 kernel; 17: 8-wave 256x256 kernel (p8); 31: 4-wave 256x256 kernel (w4) forced; 15: M <= 64 streaming
+  bool use_tr = true;           // use_tr bit 0: transposed LDS reads (attention, gemm_tn)
+  bool attn_dma = false;        // bit 1: attention forward with the LDS-DMA K/V ring
+  bool tn_w4 = true;            // bit 3 CLEARS it: 256x256 gemm_tn_w4_kernel (default) vs the 128x128 kernel
+  bool skinny8 = true;          // bit 4 CLEARS it: M <= 16 decode GEMMs: whole-cache-line form of the streaming kernel
+  int dec64_variant = 0;        // bits 5-6: 0 / 3 the whole-line streaming kernel (dec64x), 1 / 2 the LDS-ring kernel
+  int dec64x_nw = 0;            // bits 7-8: rows per workgroup of the dec64x kernel (0 = by shape, 1 / 2 / 3 = 48 / 64 / 128; tests)
+  bool sample_compact = true;   // bit 9 CLEARS it: the compact sampler (full sweeps otherwise)
+  bool w4s_few = false;         // bit 10 (tests): 8 workgroups walk the tile list, so small problems exercise long walks
+  bool w4_nodeep = false;       // bit 11 (tests, A/B): the products of >= 128 K-tiles keep the default K-loop text (round 6: they run the DEEP text)
+  bool w4_chunk_deal = false;   // bit 12 (tests, A/B): every XCD walks a contiguous chunk of the tile order (rounds 1-5) instead of the block-cyclic deal
+  bool attn_rows16 = false;     // context flag bit 8 only: the 16-row attention forward and dQ kernels at head_dim 128
+};
+KernelFlags kernel_flags(int gemm_variant, int use_tr);
+const KernelFlags& process_flags();            // the value opadpo_set_flags stored
+// what an opadpo_ctx_set_flags(gemm_variant, use_tr) word overrides of the process flags
+struct KernelOverrides {
+  int gemm_variant = -1;        // >= 0: the context's gemm_nt variant
+  bool word = false;            // use_tr >= 0: the fields below replace the process ones
+  bool use_tr = false;          // bit 0
+  bool tn_w4 = false;           // bit 3 clear
+  bool attn_rows16 = false;     // bit 8
+};
+KernelOverrides kernel_overrides(int gemm_variant, int use_tr);
+// the flags of a launch: the process flags with the context's overrides applied (evaluated per launch, so later opadpo_set_flags calls reach
+// a context that overrides nothing)
+KernelFlags resolve_flags(const KernelFlags& process, const KernelOverrides& o);
+// the first launch of a table kernel sets its dynamic-LDS limit
+inline void set_lds_once(bool& done, const void* fn, int lds) {
+  if (!done && lds > 0) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  done = true;
+}
+
 // opadpo_last_error() reporting for entry points outside capi.hip: a message -> hipErrorInvalidValue; hipSuccess -> 0, else the code + its text
 int opadpo_report_bad(const char* where, const char* what);
 int opadpo_report_done(hipError_t e, const char* where);
-bool opadpo_flag_tr();
-void opadpo_set_attn_dma(bool on);
 
 // ws / ws_bytes: workspace of the K-folded products, at least gemm_nt_workspace_bytes(a) (0 for every other problem); used in stream order
-hipError_t launch_gemm_nt(const GemmNTArgs& a, hipStream_t st, void* ws, size_t ws_bytes);
-size_t gemm_nt_workspace_bytes(const GemmNTArgs& a);
-// the launches launch_gemm_nt would make under opadpo_set_flags(gemm_variant, use_tr) on `cus` CUs, one line each: kernel grid.x grid.y block LDS
-hipError_t gemm_nt_plan_text(const GemmNTArgs& a, int gemm_variant, int use_tr, int cus, char* out, size_t out_len);
-hipError_t launch_gemm_tn(const GemmTNArgs& a, hipStream_t st);
+hipError_t launch_gemm_nt(const GemmNTArgs& a, const KernelFlags& f, hipStream_t st, void* ws, size_t ws_bytes);
+size_t gemm_nt_workspace_bytes(const GemmNTArgs& a, const KernelFlags& f);
+// the launches launch_gemm_nt would make under these flags on `cus` CUs, one line each: kernel grid.x grid.y block LDS
+hipError_t gemm_nt_plan_text(const GemmNTArgs& a, const KernelFlags& f, int cus, char* out, size_t out_len);
+hipError_t launch_gemm_tn(const GemmTNArgs& a, const KernelFlags& f, hipStream_t st);
 // all problems must share M and be eligible for the 256x256 kernel (N1, N2 % 256 == 0, q_group_n1 % 256 == 0); otherwise the
 // problems are launched one by one
-void opadpo_set_sample_compact(int on);      // 1 / 0 force, -1 = OPADPO_SAMPLE_COMPACT (default 1)
-hipError_t launch_gemm_tn_group(const GemmTNArgs* list, int n, hipStream_t st, void* workspace = nullptr, size_t workspace_bytes = 0, int* all_ordered = nullptr);
+hipError_t launch_gemm_tn_group(const GemmTNArgs* list, int n, const KernelFlags& f, hipStream_t st, void* workspace = nullptr, size_t workspace_bytes = 0,
+                                int* all_ordered = nullptr);
 // bytes of workspace that make a grouped launch of these problems deterministic (0: the problems do not run on the 256x256 kernel)
-size_t gemm_tn_group_workspace_bytes(const GemmTNArgs* list, int n);
+size_t gemm_tn_group_workspace_bytes(const GemmTNArgs* list, int n, const KernelFlags& f);
 
-hipError_t launch_attn_fwd(const AttnArgs& a, hipStream_t st);
-hipError_t launch_attn_bwd(const AttnArgs& a, hipStream_t st);
+hipError_t launch_attn_fwd(const AttnArgs& a, const KernelFlags& f, hipStream_t st);
+hipError_t launch_attn_bwd(const AttnArgs& a, const KernelFlags& f, hipStream_t st);
+// the launches launch_attn_fwd (backward = 0) or launch_attn_bwd would make under these flags, one line each: kernel grid.x block LDS
+hipError_t attn_plan_text(const AttnArgs& a, int backward, const KernelFlags& f, char* out, size_t out_len);
 
 hipError_t launch_rmsnorm_fwd(const void* x, int x_f32, const bf16_t* w, bf16_t* y, float* rstd, int rows, int H, float eps, hipStream_t st);
 hipError_t launch_rmsnorm_sum_fwd(const void* resid, int resid_f32, const float* partials, int n_partials, size_t partial_stride, const bf16_t* w,
                                   float* x_out, bf16_t* y, float* rstd, int rows, int H, float eps, hipStream_t st);
-hipError_t launch_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, hipStream_t st);
-int gemm_nt_dec64_splits(int N, int K, int splits);
+hipError_t launch_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, const KernelFlags& f, hipStream_t st);
+int gemm_nt_dec64_splits(int N, int K, int splits, const KernelFlags& f);
 hipError_t launch_rmsnorm_bwd(const bf16_t* dy, const void* x, int x_f32, const bf16_t* w, const float* rstd, const void* dres,
                               int dres_f32, float* dx_f32, bf16_t* dx_bf16, int rows, int H, hipStream_t st);
 hipError_t launch_layernorm_fwd(const void* x, const bf16_t* w, const bf16_t* b, void* y, int rows, int H, float eps, hipStream_t st, int x_f32 = 0, int y_f32 = 0);

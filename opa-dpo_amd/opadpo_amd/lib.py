@@ -163,7 +163,7 @@ def set_flags(use_glds=10, use_tr: bool = True) -> None:
     gemm_tn_w4_kernel, bit 4 = 16-row streaming kernel also for M <= 16 (default: gemm_nt_skinny8_kernel), bits 5-6 = kernel of
     opadpo_gemm_nt_decode: 0 / 3 the whole-line streaming kernel (gemm_nt_dec64x, the library's choice), 1 the LDS-ring kernel of rounds 2-4;
     bits 7-8 = weight rows per workgroup of the streaming kernel (0 by shape, 1 / 2 / 3 = 48 / 64 / 128), bit 9 = opadpo_sample runs its full
-    vocabulary sweeps (the exactness yardstick; clear: OPADPO_SAMPLE_COMPACT decides, default compact), bit 10 = the streaming 256x256 GEMM walks
+    vocabulary sweeps (the exactness yardstick; default: the compact tail), bit 10 = the streaming 256x256 GEMM walks
     its tile list on 8 workgroups (tests), bit 11 = the products of >= 128 K-tiles keep the default K-loop text (default since round 6: the DEEP text,
     bit-identical results), bit 12 = contiguous-chunk deal of the tile order to the XCDs (rounds 1-5; default since round 6: block-cyclic, bit-identical).
     NOTE: a context's use_tr (CtxEngine / opadpo_ctx_set_flags) is a different bit space above bit 4 - see include/opadpo_hip.h."""

@@ -426,6 +426,55 @@ def test_gemm_nt_routing_rule(built_lib):
     assert plan(M=40, N=4096, K1=4096, out_f32=1, R=1, act=S, var=10, tr=4097) == ["skinny<3, 1, 4, false> 256"]
 
 
+def test_attention_routing_rule(built_lib):
+    """Host-side kernel choice of the attention forward and backward, read through opadpo_debug_attn_plan (a test entry point outside the
+    header: the launches as `kernel grid.x block LDS` lines; nothing is launched).  Pins kernel, grid and LDS at the benchmark's packed ragged
+    shape (22 sequences of up to 1471 rows, 32362 rows, 32 heads of 128) and at the CLIP tower's (577 tokens, 16 heads of 64) under process
+    words 0 / 1 / 3, and a context word with bit 8: the 16-row kernels, transposed reads from the context word, the LDS-DMA forward from the
+    process word alone."""
+    lib = ctypes.CDLL(built_lib)
+    f = lib.opadpo_debug_attn_plan
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_int] * 12 + [ctypes.c_char_p, ctypes.c_int]
+
+    def plan(S, L, nh, hd, ld, ldo, rows=0, bwd=0, dq=1, dq_f32=0, tr=1, ctx=-1):
+        buf = ctypes.create_string_buffer(1024)
+        rc = f(S, L, nh, hd, ld, ldo, rows, bwd, dq, dq_f32, tr, ctx, buf, 1024)
+        return buf.value.decode().splitlines() if rc == 0 else rc
+
+    llm = dict(S=22, L=1471, nh=32, hd=128, ld=12288, ldo=4096, rows=32362)
+    fwd32, dq32 = "attn_fwd32_kernel 8448 256 65696", "attn_bwd_dq32_kernel 8448 256 65696"
+    delta = "attn_delta_kernel<128> 64724 256 0"
+    for tr in (0, 1, 3):
+        assert plan(**llm, tr=tr) == [fwd32]
+    assert plan(**llm, bwd=1) == [delta, "attn_bwd_dkdv_kernel<128, true> 16192 256 66704", dq32]
+    assert plan(**llm, bwd=1, dq_f32=1) == [delta, "attn_bwd_dkdv_kernel<128, true> 16192 256 66704", "attn_bwd_dq_kernel<128, true> 16192 256 0"]
+    assert plan(**llm, bwd=1, dq=0, dq_f32=1) == [delta, "attn_bwd_dkdv_kernel<128, true> 16192 256 66704", "attn_bwd_dq_kernel<128, true> 16192 256 0"]
+    assert plan(**llm, bwd=1, tr=0) == [delta, "attn_bwd_dkdv_kernel<128, false> 16192 256 66704", dq32]
+    assert plan(**llm, bwd=1, tr=0, dq_f32=1) == [delta, "attn_bwd_dkdv_kernel<128, false> 16192 256 66704", "attn_bwd_dq_kernel<128, false> 16192 256 0"]
+    assert plan(**llm, bwd=1, tr=3) == [delta, "attn_bwd_dkdv_kernel<128, true> 16192 256 66704", dq32]
+    # context bit 8: the 16-row forward and dQ; transposed reads from the context word (bit 0), the DMA ring from the process word (bit 1)
+    assert plan(**llm, tr=3, ctx=256) == ["attn_fwd_kernel<128, false, true> 16192 256 65696"]
+    assert plan(**llm, tr=3, ctx=257) == ["attn_fwd_kernel<128, true, true> 16192 256 65696"]
+    assert plan(**llm, tr=1, ctx=258) == ["attn_fwd_kernel<128, false, false> 16192 256 32848"]
+    assert plan(**llm, tr=0, ctx=257) == ["attn_fwd_kernel<128, true, false> 16192 256 32848"]
+    assert plan(**llm, tr=3, ctx=256, bwd=1) == [delta, "attn_bwd_dkdv_kernel<128, false> 16192 256 66704", "attn_bwd_dq_kernel<128, false> 16192 256 0"]
+    assert plan(**llm, tr=0, ctx=1) == [fwd32]
+    assert plan(**llm, tr=0, ctx=1, bwd=1) == [delta, "attn_bwd_dkdv_kernel<128, true> 16192 256 66704", dq32]
+    # padded rows: the delta pass covers S * L rows
+    assert plan(S=2, L=1087, nh=32, hd=128, ld=12288, ldo=4096, bwd=1)[0] == "attn_delta_kernel<128> 4348 256 0"
+    clip = dict(S=22, L=577, nh=16, hd=64, ld=3072, ldo=1024)
+    assert plan(**clip) == ["attn_fwd_kernel<64, true, false> 3520 256 16464"]
+    assert plan(**clip, tr=0) == ["attn_fwd_kernel<64, false, false> 3520 256 16464"]
+    assert plan(**clip, tr=3) == ["attn_fwd_kernel<64, true, true> 3520 256 32928"]
+    assert plan(**clip, tr=3, ctx=256) == ["attn_fwd_kernel<64, false, true> 3520 256 32928"]
+    assert plan(**clip, bwd=1) == ["attn_delta_kernel<64> 6347 256 0", "attn_bwd_dkdv_kernel<64, true> 3520 256 33936", "attn_bwd_dq_kernel<64, true> 3520 256 0"]
+    # per-sequence extents past 2e9 bytes: the forward leaves the 32-row kernel and the DMA ring, the backward refuses
+    assert plan(S=1, L=100000, nh=32, hd=128, ld=12288, ldo=4096, tr=3) == ["attn_fwd_kernel<128, true, false> 50016 256 32848"]
+    assert plan(S=1, L=100000, nh=32, hd=128, ld=12288, ldo=4096, bwd=1) != 0 and plan(**dict(llm, hd=96)) != 0
+    assert plan(**dict(llm, S=0)) == [] and plan(**dict(llm, L=0), bwd=1) == []
+
+
 def test_generated_kloop_is_current():
     """opa-dpo_amd/csrc/w4_kloop.inc (the K-loop of gemm_nt_w4_kernel as an asm block) is generated: the committed file must be what the
     committed generator emits, and the generator's hazard checks (LDS stage reuse, fragment registers, M0, vmcnt bookkeeping) must hold."""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # decode ms/step of the rollout (tools/rollout_bench.py) for several library builds / batch sizes on one box
-#   tools/ab_rollout.sh "8 16 32 64" new prev          (OPADPO_DEC64_MIN etc. pass through)
+#   tools/ab_rollout.sh "8 16 32 64" new prev          (the RB_* settings of tools/rollout_bench.py pass through)
 BS=$1; shift
 for B in $BS; do
   for L in "$@"; do

@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of environment-switched variants on the WHOLE optimizer step (bench.py, 10 steps after 3 warm-up, no side legs), interleaved:
-#   AB_CONFIGS="X=0 OPADPO_EW_NT=1 OPADPO_FUSE_RESID=0" tools/ab_step_env.sh     (each config: comma-separated VAR=value pairs)
+#   AB_CONFIGS="X=0 OPADPO_BENCH_PAIRS=20" tools/ab_step_env.sh     (each config: comma-separated VAR=value pairs)
 B="python bench.py --steps ${AB_STEPS:-10} --warmup 3 --no-cpu-baseline --no-rollout --no-exchange-probe --no-side-legs ${AB_ARGS:-}"
 P='import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print("%.3f pairs/s  %.1f ms  frac %.4f" % (r["value"], r["ms_per_step"], r["roofline"]["frac"]))'
 mkdir -p gpurun_out
