@@ -267,6 +267,30 @@ int opadpo_sample(const float* logits, int ldl, int rows, int V, float temperatu
                   uint64_t seed, uint64_t step, const int32_t* step_ptr, uint8_t* finished, int pad_id, int eos_id,
                   int32_t* out, int32_t* history, void* stream);
 
+/* Beam search (HF GenerationMixin._beam_search with do_sample=False, num_return_sequences=1, length_penalty=1.0, early_stopping=False).
+ * B items of k beams each; rows = B*k <= 64, 1 <= k <= OPADPO_MAX_BEAMS.  Row i is beam i % k of item i / k.
+ * Decode attention of the beam rows: the items' prefix caches [B, nh, Lp, hd] (prefix_mask [B, Lp], nullable) are shared by their beams;
+ * suffix caches [B*k, nh, max_new, hd]: the key at position j >= Lp of row i lives in physical row table[i][j - Lp] ([B*k, max_new] int32).
+ * The new token (position pos_ptr[0] >= Lp) is rotated and appended at (i, pos - Lp).  Bit-identical to opadpo_attn_decode_fused on the
+ * materialised per-row cache (workspace: opadpo_attn_decode_workspace_bytes(B*k, nh, hd, Lp + max_new)). */
+#define OPADPO_MAX_BEAMS 16
+int opadpo_attn_decode_beam(const uint16_t* qkv, int ld, const float* cos_tab, const float* sin_tab, const uint16_t* k_prefix,
+                            const uint16_t* v_prefix, uint16_t* k_suffix, uint16_t* v_suffix, uint16_t* o, const uint8_t* prefix_mask, int B, int k,
+                            int nh, int hd, const int32_t* pos_ptr, int Lp, int max_new, const int32_t* table, float scale, void* workspace,
+                            size_t workspace_bytes, void* stream);
+/* One beam-search step at step index `step` (0 = the first generated token: only beam 0 of an item is live) on fp32 logits [B*k, V] (ldl
+ * apart).  Candidates are ranked by log_softmax + beam score, ties to the lower flat index beam*V + token.  Caller-owned device state, all
+ * zero-initialised before step 0 except as noted:
+ *   run_score [B*k] f32 running beam scores;  cand_val [B*k*2k] f32, cand_tok [B*k*2k] int32 scratch;
+ *   fin_score [B*k] f32, fin_info [3][B*k] int32 (step, parent row, token), fin_n [B] int32: per item the best k finished hypotheses,
+ *     sorted, score = sum logprob / generated length (EOS included);  done [B] uint8 (early stop or last step);
+ *   cur_tok [B*k] int32 the running beams' newest tokens;  bp [2][max_new][B*k] int32 backpointers (parent row | token) per step;
+ *   table [2][B*k][max_new] int32 slot tables by step parity: step t reads buffer t & 1 and writes buffer (t + 1) & 1.
+ * A candidate is finished if its token is eos_id (>= 0) or step == max_new - 1. */
+int opadpo_beam_step(const float* logits, int ldl, int B, int k, int V, int step, int max_new, int eos_id, int pad_id, float* run_score,
+                     float* cand_val, int32_t* cand_tok, float* fin_score, int32_t* fin_info, int32_t* fin_n, uint8_t* done, int32_t* cur_tok,
+                     int32_t* bp, int32_t* table, void* stream);
+
 /* =====================================================================================================================
  * Context API: the SEQUENCE-LEVEL entry points.
  *
@@ -413,9 +437,18 @@ int opadpo_decode_step(opadpo_ctx* ctx, void* stream);
  * them; measured faster than graph replay on MI355X: 3.45 vs 3.72 ms per step at 7B / 4 sequences); use_graph = 1: one step is
  * captured into a hipGraph once and replayed per token (same tokens, bit for bit) */
 int opadpo_decode_run(opadpo_ctx* ctx, int n_steps, int use_graph, void* stream);
-/* synchronous: *all_finished = every row has emitted EOS */
+/* synchronous: *all_finished = every row has emitted EOS (beam decode: every item is done) */
 int opadpo_decode_all_finished(opadpo_ctx* ctx, int* all_finished, void* stream);
 int opadpo_decode_end(opadpo_ctx* ctx);
+/* model.generate(num_beams=k, do_sample=False) (eval_llava_rlhf_coco/model_vqa.py): ONE prefill of the B questions (its KV cache is the
+ * items' shared prefix), the k beams' generated keys in per-row suffix caches addressed by a slot table, and step 0 from the prefill logits.
+ * opadpo_decode_step / _run / _all_finished / _end then work on the beam decode (B*k rows; selection on the device, nothing read back).
+ * 1 <= k <= OPADPO_MAX_BEAMS, B*k <= 64, vocab >= 2k. */
+int opadpo_decode_beam_begin(opadpo_ctx* ctx, int adapter_id, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats, int B, int Q,
+                             int k, int max_new_tokens, int eos_id, int pad_id, void* stream);
+/* synchronous: the best hypothesis per item into tokens [B, max_new_tokens] int32 (EOS kept, pad after it) and its score into scores [B]
+ * fp32 (both device memory).  An item that is not done when this is called takes its running beams as finished (as a last step would). */
+int opadpo_decode_beam_result(opadpo_ctx* ctx, int32_t* tokens, float* scores, void* stream);
 
 #ifdef __cplusplus
 }

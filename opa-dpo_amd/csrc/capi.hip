@@ -408,6 +408,30 @@ int opadpo_attn_decode_fused(const uint16_t* qkv, int ld, const float* cos_tab, 
                                        workspace, workspace_bytes, S(stream)),
               "opadpo_attn_decode_fused");
 }
+int opadpo_attn_decode_beam(const uint16_t* qkv, int ld, const float* cos_tab, const float* sin_tab, const uint16_t* k_prefix,
+                            const uint16_t* v_prefix, uint16_t* k_suffix, uint16_t* v_suffix, uint16_t* o, const uint8_t* prefix_mask, int B, int k,
+                            int nh, int hd, const int32_t* pos_ptr, int Lp, int max_new, const int32_t* table, float scale, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  const char* fn = "opadpo_attn_decode_beam";
+  if (!qkv || !cos_tab || !sin_tab || !k_prefix || !v_prefix || !k_suffix || !v_suffix || !o || !pos_ptr || !table) return bad(fn, "null operand");
+  if (B <= 0 || k <= 0 || k > OPADPO_MAX_BEAMS || Lp <= 0 || max_new <= 0) return bad(fn, "bad shape");
+  if (ld % 8 || ld < 3 * nh * hd) return bad(fn, "qkv rows must hold [q|k|v] with an aligned leading dimension");
+  return done(launch_attn_decode_beam(qkv, ld, cos_tab, sin_tab, k_prefix, v_prefix, k_suffix, v_suffix, o, prefix_mask, B, k, nh, hd, pos_ptr, Lp,
+                                      max_new, table, 0, scale, workspace, workspace_bytes, S(stream)),
+              fn);
+}
+int opadpo_beam_step(const float* logits, int ldl, int B, int k, int V, int step, int max_new, int eos_id, int pad_id, float* run_score,
+                     float* cand_val, int32_t* cand_tok, float* fin_score, int32_t* fin_info, int32_t* fin_n, uint8_t* done_, int32_t* cur_tok,
+                     int32_t* bp, int32_t* table, void* stream) {
+  const char* fn = "opadpo_beam_step";
+  if (!logits || !run_score || !cand_val || !cand_tok || !fin_score || !fin_info || !fin_n || !done_ || !cur_tok || !bp || !table) return bad(fn, "null operand");
+  if (B <= 0 || k <= 0 || k > OPADPO_MAX_BEAMS) return bad(fn, "num_beams must be in 1..OPADPO_MAX_BEAMS");
+  if (B * k > 64) return bad(fn, "B * num_beams above 64 rows");
+  if (V < 2 * k || V > 32768 || ldl < V) return bad(fn, "vocabulary must hold 2 * num_beams .. 32768 tokens");
+  if (step < 0 || step >= max_new) return bad(fn, "step out of range");
+  const BeamState s{run_score, cand_val, cand_tok, fin_score, fin_info, fin_n, done_, cur_tok, bp, table, (long long)B * k * max_new};
+  return done(launch_beam_step(logits, ldl, 1, B, k, V, max_new, eos_id, pad_id, nullptr, step, s, S(stream)), fn);
+}
 int opadpo_rope_kv_append(uint16_t* qkv, int ld, const float* cos_tab, const float* sin_tab, uint16_t* k_cache, uint16_t* v_cache,
                           int B, int nh, int hd, const int32_t* pos_ptr, int max_ctx, void* stream) {
   return done(launch_rope_kv_append(qkv, ld, cos_tab, sin_tab, k_cache, v_cache, B, nh, hd, pos_ptr, max_ctx, S(stream)),

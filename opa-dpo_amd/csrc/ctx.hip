@@ -269,6 +269,9 @@ struct opadpo_ctx {
     float *hb, *rstd, *logits; int32_t *cur_tok, *step_d, *pos_d; uint8_t* finished; void* ws; size_t ws_bytes;
     float *part_o, *part_d; int split_o = 1, split_d = 1; bool use64 = false;      // K-split partial tiles of the 9..64-token decode GEMMs
     int32_t* history; float temperature; int top_k; float top_p; uint64_t seed; int eos_id, pad_id, suppress_eos;
+    // beam decode (opadpo_decode_beam_begin): B = items * beams rows; kc / vc = the items' prefix caches [items, nh, Lp, hd], ks / vs = the
+    // rows' suffix caches [B, nh, max_new, hd]; finished = per-item done flags; bs = selection state (decode.hip beam_update_kernel)
+    int beams = 0, items = 0; bf16_t *ks = nullptr, *vs = nullptr; BeamState bs{};
     hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; hipStream_t cap_stream = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;
   } dec;
 };
@@ -1198,17 +1201,25 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
 }
 
 // ---- rollout: prefill + KV-cache decode (generate.py; online_generator.py:292-309) ----------------------------------------------
-static hipError_t decode_head(opadpo_ctx* c, const float* src_f32, const float* partials, int n_partials, hipStream_t st) {
+// rows = D.B, or the items of a beam decode for its step 0 (the prefill's last rows; every beam of an item reads the item's logits row)
+static hipError_t decode_head(opadpo_ctx* c, const float* src_f32, const float* partials, int n_partials, hipStream_t st, int rows = -1) {
   opadpo_ctx::Decode& D = c->dec;
   const opadpo_dims& d = c->d;
+  if (rows < 0) rows = D.B;
   hipError_t e;
   if (n_partials > 0) {
-    if ((e = launch_rmsnorm_sum_fwd(src_f32, 1, partials, n_partials, (size_t)D.B * d.hidden, c->norm, D.x2, D.hn, D.rstd, D.B, d.hidden, d.rms_eps, st)) != hipSuccess) return e;
-  } else if ((e = launch_rmsnorm_fwd(src_f32, 1, c->norm, D.hn, D.rstd, D.B, d.hidden, d.rms_eps, st)) != hipSuccess) return e;
-  GemmNTArgs g = gemm(D.hn, d.hidden, c->lm_head, d.hidden, d.hidden, D.logits, d.vocab, 1, D.B, d.vocab); g.act |= OPADPO_GEMM_STREAM;
-  if (D.use64) e = launch_gemm_nt_dec64(g, 1, 1, ctx_flags(c), st);
+    if ((e = launch_rmsnorm_sum_fwd(src_f32, 1, partials, n_partials, (size_t)D.B * d.hidden, c->norm, D.x2, D.hn, D.rstd, rows, d.hidden, d.rms_eps, st)) != hipSuccess) return e;
+  } else if ((e = launch_rmsnorm_fwd(src_f32, 1, c->norm, D.hn, D.rstd, rows, d.hidden, d.rms_eps, st)) != hipSuccess) return e;
+  GemmNTArgs g = gemm(D.hn, d.hidden, c->lm_head, d.hidden, d.hidden, D.logits, d.vocab, 1, rows, d.vocab); g.act |= OPADPO_GEMM_STREAM;
+  if (D.use64 && rows == D.B) e = launch_gemm_nt_dec64(g, 1, 1, ctx_flags(c), st);
   else e = run_gemm(c, g, st);
   if (e != hipSuccess) return e;
+  if (D.beams) {
+    if ((e = launch_beam_step(D.logits, d.vocab, rows == D.B ? 1 : D.beams, D.items, D.beams, d.vocab, D.max_new, D.eos_id, D.pad_id, D.step_d, 0, D.bs,
+                              st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(add_i32_kernel, dim3(1), dim3(64), 0, st, D.step_d, 1);
+    return hipGetLastError();
+  }
   if (D.suppress_eos) {
     hipLaunchKernelGGL(set_column_f32_kernel, g1(D.B), dim3(256), 0, st, D.logits, d.vocab, D.B, D.eos_id, -INFINITY);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -1227,6 +1238,18 @@ static hipError_t decode_one(opadpo_ctx* c, hipStream_t st) {
   const opadpo_ctx::Adapter& ad = c->adapters[D.adapter];
   const LoraOff o = lora_off(d);
   hipError_t e;
+  // layer i's decode attention: one cache per row, or (beam decode) the items' prefix caches + the rows' suffix caches through the slot table
+  auto attn = [&](int i) -> hipError_t {
+    const float scale = 1.0f / sqrtf((float)hd);
+    if (D.beams) {
+      const size_t pre = (size_t)D.items * nh * D.Lp * hd, suf = (size_t)B * nh * D.max_new * hd;
+      return launch_attn_decode_beam(D.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * pre, D.vc + i * pre, D.ks + i * suf, D.vs + i * suf, D.att, D.key_mask,
+                                     D.items, D.beams, nh, hd, D.pos_d, D.Lp, D.max_new, D.bs.table, D.bs.table_stride, scale, D.ws, D.ws_bytes, st);
+    }
+    const size_t per_layer = (size_t)B * nh * D.max_ctx * hd;
+    return launch_attn_decode_fused(D.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * per_layer, D.vc + i * per_layer, D.att, D.key_mask, B, nh, hd, D.pos_d,
+                                    D.max_ctx, scale, D.ws, D.ws_bytes, st);
+  };
   hipLaunchKernelGGL(add_i32_kernel, dim3(1), dim3(64), 0, st, D.pos_d, 1);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = launch_gather_rows(c->embed, H, D.cur_tok, D.emb, B, H, st)) != hipSuccess) return e;
@@ -1246,9 +1269,7 @@ static hipError_t decode_one(opadpo_ctx* c, hipStream_t st) {
       else e = launch_rmsnorm_sum_fwd(D.hb, 1, D.part_d, D.split_d, pstride, w0.ln1, D.x, D.n1, D.rstd, B, H, d.rms_eps, st);
       if (e != hipSuccess) return e;
       if ((e = dg(D.n1, H, w.wqkv, H, D.qkv, 3 * H, 3 * H, 0, 1)) != hipSuccess) return e;
-      const size_t per_layer = (size_t)B * nh * D.max_ctx * hd;
-      if ((e = launch_attn_decode_fused(D.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * per_layer, D.vc + i * per_layer, D.att, D.key_mask, B, nh, hd, D.pos_d,
-                                        D.max_ctx, 1.0f / sqrtf((float)hd), D.ws, D.ws_bytes, st)) != hipSuccess) return e;
+      if ((e = attn(i)) != hipSuccess) return e;
       if ((e = dg(D.att, H, w.wo, H, D.part_o, H, H, 1, D.split_o)) != hipSuccess) return e;
       if ((e = launch_rmsnorm_sum_fwd(D.x, 1, D.part_o, D.split_o, pstride, w0.ln2, D.hb, D.n2, D.rstd, B, H, d.rms_eps, st)) != hipSuccess) return e;
       if (ad.kind == 2 && ad.swiglu_pair) {
@@ -1279,9 +1300,7 @@ static hipError_t decode_one(opadpo_ctx* c, hipStream_t st) {
       GemmNTArgs g2 = gemm(D.n1, H, w.wqkv, H, H, D.qkv, 3 * H, 0, B, 3 * H); g2.act |= OPADPO_GEMM_STREAM;
       if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
     }
-    const size_t per_layer = (size_t)B * nh * D.max_ctx * hd;
-    if ((e = launch_attn_decode_fused(D.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * per_layer, D.vc + i * per_layer, D.att, D.key_mask, B, nh, hd, D.pos_d,
-                                      D.max_ctx, 1.0f / sqrtf((float)hd), D.ws, D.ws_bytes, st)) != hipSuccess) return e;
+    if ((e = attn(i)) != hipSuccess) return e;
     if (lw) {
       GemmNTArgs g3 = gemm(D.att, H, lw + o.a_o, H, H, D.t_o, r, 0, B, r); g3.alpha = s; g3.act |= OPADPO_GEMM_STREAM;
       if ((e = run_gemm(c, g3, st)) != hipSuccess) return e;
@@ -1298,25 +1317,22 @@ static hipError_t decode_one(opadpo_ctx* c, hipStream_t st) {
   return decode_head(c, (const float*)cur, nullptr, 0, st);
 }
 
-int opadpo_decode_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats, int B, int Q,
-                        int max_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, int eos_id, int pad_id, int suppress_eos,
-                        int32_t* history, void* stream) {
-  if (!c) return (int)hipErrorInvalidValue;
-  if (!weights_ready(c)) return cbad(c, __func__, "LLM weights not set");
-  if (adapter_id < 0 || adapter_id >= OPADPO_MAX_ADAPTERS) return cbad(c, __func__, "adapter id out of range");
-  if (!ids || !text_mask || !feats || !history || B <= 0 || Q <= 0 || max_new_tokens <= 0 || temperature <= 0.f) return cbad(c, __func__, "null operand or bad shape");
-  if (B > 64) return cbad(c, __func__, "decode batch above 64 per device is not supported by the weight-streaming GEMMs");
-  opadpo_decode_end(c);
-  hipStream_t st = (hipStream_t)stream;
+// beams = 0: sampling rollout of B rows; beams = k: beam search over B items x k rows (the prefill runs on the B items only)
+static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats, int items,
+                             int Q, int beams, int max_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, int eos_id, int pad_id,
+                             int suppress_eos, int32_t* history, hipStream_t st) {
   const opadpo_dims& d = c->d;
   const opadpo_ctx::Adapter& ad = c->adapters[adapter_id];
   const int side = d.image_size / d.patch, P = side * side, H = d.hidden, F = d.ffn, r = d.lora_r, nh = d.n_heads, hd = d.head_dim, V = d.vocab;
-  const int Lp = Q + P - 1, max_ctx = Lp + max_new_tokens, M = B * Lp;
+  const int B = beams ? items * beams : items;           // decode rows
+  const int Lp = Q + P - 1, max_ctx = Lp + max_new_tokens, M = items * Lp;
+  const int kv_len = beams ? Lp : max_ctx;                // cache slots per prefill sequence
   CK(ensure_rope(c, max_ctx, st));
   opadpo_ctx::Decode& D = c->dec;
   D.B = B; D.Lp = Lp; D.max_ctx = max_ctx; D.adapter = adapter_id; D.max_new = max_new_tokens;
   D.history = history; D.temperature = temperature; D.top_k = top_k; D.top_p = top_p; D.seed = seed; D.eos_id = eos_id; D.pad_id = pad_id;
   D.suppress_eos = suppress_eos;
+  D.beams = beams; D.items = items;
   D.ws_bytes = attn_decode_workspace_bytes(B, nh, hd, max_ctx);
   // 9..64 sequences without LoRA tails (adapter-free or merged adapter): the decode GEMM for <= 64 tokens (gemm_nt_dec64x_kernel), the o / down
   // projections K-split into fp32 partial tiles that the following RMSNorm adds.  Measured per decode step against the 8/16-row streaming kernels
@@ -1326,8 +1342,16 @@ int opadpo_decode_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const
   D.split_d = D.use64 ? gemm_nt_dec64_splits(H, F, 0, ctx_flags(c)) : 1;
   auto layout = [&](void* base) {
     Carve cv(base);
-    const size_t kvn = (size_t)d.n_layers * B * nh * max_ctx * hd;
-    D.kc = cv.take<bf16_t>(kvn); D.vc = cv.take<bf16_t>(kvn); D.key_mask = cv.take<uint8_t>((size_t)B * max_ctx);
+    const size_t kvn = (size_t)d.n_layers * items * nh * kv_len * hd;
+    D.kc = cv.take<bf16_t>(kvn); D.vc = cv.take<bf16_t>(kvn); D.key_mask = cv.take<uint8_t>((size_t)items * kv_len);
+    if (beams) {
+      const size_t sn = (size_t)d.n_layers * B * nh * max_new_tokens * hd, K2 = 2 * (size_t)beams;
+      D.ks = cv.take<bf16_t>(sn); D.vs = cv.take<bf16_t>(sn);
+      BeamState& s = D.bs;
+      s.run_score = cv.take<float>(B); s.cand_val = cv.take<float>(B * K2); s.cand_tok = cv.take<int32_t>(B * K2); s.fin_score = cv.take<float>(B);
+      s.fin_info = cv.take<int32_t>(3 * (size_t)B); s.fin_n = cv.take<int32_t>(items); s.done = cv.take<uint8_t>(items);
+      s.bp = cv.take<int32_t>(2 * (size_t)max_new_tokens * B); s.table_stride = (long long)B * max_new_tokens; s.table = cv.take<int32_t>(2 * (size_t)s.table_stride);
+    }
     D.x = cv.take<float>((size_t)B * H); D.x2 = cv.take<float>((size_t)B * H); D.hs = cv.take<float>((size_t)B * H); D.hn = cv.take<bf16_t>((size_t)B * H);
     D.n1 = cv.take<bf16_t>((size_t)B * H); D.qkv = cv.take<bf16_t>((size_t)B * 3 * H); D.t_qkv = cv.take<bf16_t>((size_t)B * 3 * r);
     D.att = cv.take<bf16_t>((size_t)B * H); D.t_o = cv.take<bf16_t>((size_t)B * r); D.hb = cv.take<float>((size_t)B * H); D.n2 = cv.take<bf16_t>((size_t)B * H);
@@ -1343,19 +1367,20 @@ int opadpo_decode_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const
   D.arena = ctx_alloc(c, D.bytes, st);
   if (!D.arena) return cfail(c, hipErrorOutOfMemory, "opadpo_decode_begin (KV cache)");
   layout(D.arena);
+  if (beams) { D.bs.cur_tok = D.cur_tok; D.finished = D.bs.done; }       // a beam decode's finished flags are its items' done flags
   D.active = true;
   // ---- prefill through the full-sequence kernels (scratch arena released afterwards) ----
   opadpo_saved pf;
-  pf.S = B; pf.L = Lp; pf.T = 1; pf.K = 1; pf.M = M; pf.R = B; pf.train = 0; pf.nb = 1;
+  pf.S = items; pf.L = Lp; pf.T = 1; pf.K = 1; pf.M = M; pf.R = items; pf.train = 0; pf.nb = 1;
   size_t pbytes = 0;
   auto playout = [&](void* base) {
     Carve cv(base);
     pf.x = cv.take<float>(3 * (size_t)M * H); pf.n1 = cv.take<bf16_t>((size_t)M * H); pf.rstd1 = cv.take<float>(M); pf.qkv = cv.take<bf16_t>((size_t)M * 3 * H);
-    pf.t_qkv = cv.take<bf16_t>((size_t)M * 3 * r); pf.attn = cv.take<bf16_t>((size_t)M * H); pf.lse = cv.take<float>((size_t)B * nh * Lp);
+    pf.t_qkv = cv.take<bf16_t>((size_t)M * 3 * r); pf.attn = cv.take<bf16_t>((size_t)M * H); pf.lse = cv.take<float>((size_t)items * nh * Lp);
     pf.t_o = cv.take<bf16_t>((size_t)M * r); pf.h = cv.take<float>((size_t)M * H); pf.n2 = cv.take<bf16_t>((size_t)M * H); pf.rstd2 = cv.take<float>(M);
     pf.t_gu = cv.take<bf16_t>((size_t)M * 2 * r); pf.gu = cv.take<bf16_t>((size_t)M * 2 * F); pf.act = cv.take<bf16_t>((size_t)M * F); pf.t_d = cv.take<bf16_t>((size_t)M * r);
-    pf.key_mask = cv.take<uint8_t>((size_t)B * Lp); pf.rows = cv.take<int32_t>(B);
-    pf.labels = cv.take<int32_t>(B);              // reused as feat_row = arange(B): every prompt carries its own image
+    pf.key_mask = cv.take<uint8_t>((size_t)items * Lp); pf.rows = cv.take<int32_t>(items);
+    pf.labels = cv.take<int32_t>(items);          // reused as feat_row = arange(items): every prompt carries its own image
     return cv.off;
   };
   pbytes = playout(nullptr);
@@ -1365,14 +1390,17 @@ int opadpo_decode_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const
 #define CKD(expr)                                                                                         \
   do {                                                                                                    \
     hipError_t e_ = (expr);                                                                               \
-    if (e_ != hipSuccess) { ctx_free(c, parena, pbytes); opadpo_decode_end(c); return cfail(c, e_, __func__); } \
+    if (e_ != hipSuccess) { ctx_free(c, parena, pbytes); opadpo_decode_end(c); return cfail(c, e_, fn); } \
   } while (0)
-  hipLaunchKernelGGL(affine_index_kernel, g1(B), dim3(256), 0, st, pf.labels, B, 1, 0);       // feat_row = arange(B)
+  hipLaunchKernelGGL(affine_index_kernel, g1(items), dim3(256), 0, st, pf.labels, items, 1, 0);       // feat_row = arange(items)
   CKD(hipGetLastError());
-  CKD(launch_embed_splice(ids, text_mask, c->embed, feats, pf.labels, nullptr, pf.x, 1, pf.key_mask, B, Q, P, H, OPADPO_IMAGE_TOKEN, st));
-  hipLaunchKernelGGL(decode_mask_kernel, g1((size_t)B * max_ctx), dim3(256), 0, st, pf.key_mask, D.key_mask, B, Lp, max_ctx);
-  CKD(hipGetLastError());
-  const size_t MH = (size_t)M * H, per_layer = (size_t)B * nh * max_ctx * hd;
+  CKD(launch_embed_splice(ids, text_mask, c->embed, feats, pf.labels, nullptr, pf.x, 1, pf.key_mask, items, Q, P, H, OPADPO_IMAGE_TOKEN, st));
+  if (beams) CKD(hipMemcpyAsync(D.key_mask, pf.key_mask, (size_t)items * Lp, hipMemcpyDeviceToDevice, st));    // the prefix mask; suffix keys are all visible
+  else {
+    hipLaunchKernelGGL(decode_mask_kernel, g1((size_t)B * max_ctx), dim3(256), 0, st, pf.key_mask, D.key_mask, B, Lp, max_ctx);
+    CKD(hipGetLastError());
+  }
+  const size_t MH = (size_t)M * H, per_layer = (size_t)items * nh * kv_len * hd;
   const LayerBufs pb = slot(d, &pf, 0);
   float* const Yp = pf.x + 2 * MH;
   const float* yin = nullptr;
@@ -1380,29 +1408,120 @@ int opadpo_decode_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const
   const float* xin = pf.x;
   for (int i = 0; i < d.n_layers; ++i) {
     float* const xo = fr ? pf.x + (size_t)((i + 1) & 1) * MH : Yp;
-    CKD(layer_fwd(c, i, ad, fr ? xin : (i == 0 ? pf.x : pb.h), yin, pf.x + (size_t)(i & 1) * MH, xo, pb, B, Lp, pf.key_mask, 0, 0, D.kc + i * per_layer,
-                  D.vc + i * per_layer, max_ctx, st));
+    CKD(layer_fwd(c, i, ad, fr ? xin : (i == 0 ? pf.x : pb.h), yin, pf.x + (size_t)(i & 1) * MH, xo, pb, items, Lp, pf.key_mask, 0, 0, D.kc + i * per_layer,
+                  D.vc + i * per_layer, kv_len, st));
     if (fr) xin = xo; else yin = Yp;
   }
-  hipLaunchKernelGGL(affine_index_kernel, g1(B), dim3(256), 0, st, pf.rows, B, Lp, Lp - 1);
+  hipLaunchKernelGGL(affine_index_kernel, g1(items), dim3(256), 0, st, pf.rows, items, Lp, Lp - 1);
   CKD(hipGetLastError());
-  if (fr) CKD(launch_gather_rows((const bf16_t*)xin, 2 * H, pf.rows, (bf16_t*)D.hs, B, 2 * H, st));   // last position of the last layer's output
+  if (fr) CKD(launch_gather_rows((const bf16_t*)xin, 2 * H, pf.rows, (bf16_t*)D.hs, items, 2 * H, st));   // last position of the last layer's output
   else {
-  CKD(launch_gather_rows((const bf16_t*)pb.h, 2 * H, pf.rows, (bf16_t*)D.hs, B, 2 * H, st));          // last position: x = h + y, added by the head's norm
-  CKD(launch_gather_rows((const bf16_t*)Yp, 2 * H, pf.rows, (bf16_t*)D.x, B, 2 * H, st));
+  CKD(launch_gather_rows((const bf16_t*)pb.h, 2 * H, pf.rows, (bf16_t*)D.hs, items, 2 * H, st));          // last position: x = h + y, added by the head's norm
+  CKD(launch_gather_rows((const bf16_t*)Yp, 2 * H, pf.rows, (bf16_t*)D.x, items, 2 * H, st));
   }
-  CKD(hipMemsetAsync(D.finished, 0, B, st));
+  CKD(hipMemsetAsync(D.finished, 0, beams ? items : B, st));
   CKD(hipMemsetAsync(D.step_d, 0, sizeof(int32_t), st));
+  if (beams) {
+    const BeamState& s = D.bs;
+    CKD(hipMemsetAsync(s.fin_n, 0, items * sizeof(int32_t), st));
+    CKD(hipMemsetAsync(s.table, 0, 2 * (size_t)s.table_stride * sizeof(int32_t), st));
+    CKD(hipMemsetAsync(s.bp, 0, 2 * (size_t)max_new_tokens * B * sizeof(int32_t), st));
+  }
   { const int32_t p0 = Lp - 1; CKD(hipMemcpyAsync(D.pos_d, &p0, sizeof(int32_t), hipMemcpyHostToDevice, st)); CKD(hipStreamSynchronize(st)); }
   // history [max_new, B] starts as pad
-  {
+  if (history) {
     std::vector<int32_t> pad((size_t)max_new_tokens * B, pad_id);
     CKD(hipMemcpyAsync(history, pad.data(), pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     CKD(hipStreamSynchronize(st));
   }
-  CKD(fr ? decode_head(c, D.hs, nullptr, 0, st) : decode_head(c, D.hs, D.x, 1, st));          // token 0 from the prefill logits
+  // token 0 from the prefill logits (beam decode: step 0 of the search on the items' rows)
+  CKD(fr ? decode_head(c, D.hs, nullptr, 0, st, items) : decode_head(c, D.hs, D.x, 1, st, items));
 #undef CKD
   ctx_free(c, parena, pbytes);
+  return 0;
+}
+
+int opadpo_decode_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats, int B, int Q,
+                        int max_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, int eos_id, int pad_id, int suppress_eos,
+                        int32_t* history, void* stream) {
+  if (!c) return (int)hipErrorInvalidValue;
+  if (!weights_ready(c)) return cbad(c, __func__, "LLM weights not set");
+  if (adapter_id < 0 || adapter_id >= OPADPO_MAX_ADAPTERS) return cbad(c, __func__, "adapter id out of range");
+  if (!ids || !text_mask || !feats || !history || B <= 0 || Q <= 0 || max_new_tokens <= 0 || temperature <= 0.f) return cbad(c, __func__, "null operand or bad shape");
+  if (B > 64) return cbad(c, __func__, "decode batch above 64 per device is not supported by the weight-streaming GEMMs");
+  opadpo_decode_end(c);
+  return decode_begin_impl(c, __func__, adapter_id, ids, text_mask, feats, B, Q, 0, max_new_tokens, temperature, top_k, top_p, seed, eos_id, pad_id,
+                           suppress_eos, history, (hipStream_t)stream);
+}
+
+int opadpo_decode_beam_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats, int B, int Q,
+                             int k, int max_new_tokens, int eos_id, int pad_id, void* stream) {
+  if (!c) return (int)hipErrorInvalidValue;
+  if (k < 1 || k > OPADPO_MAX_BEAMS) return cbad(c, __func__, "num_beams must be in 1..OPADPO_MAX_BEAMS (16)");
+  if (B <= 0 || B * k > 64) return cbad(c, __func__, "B * num_beams above 64 rows is not supported by the decode GEMMs");
+  if (!weights_ready(c)) return cbad(c, __func__, "LLM weights not set");
+  if (adapter_id < 0 || adapter_id >= OPADPO_MAX_ADAPTERS) return cbad(c, __func__, "adapter id out of range");
+  if (!ids || !text_mask || !feats || Q <= 0 || max_new_tokens <= 0) return cbad(c, __func__, "null operand or bad shape");
+  if (c->d.vocab < 2 * k || c->d.vocab > 32768) return cbad(c, __func__, "beam search needs 2 * num_beams <= vocab <= 32768");
+  opadpo_decode_end(c);
+  return decode_begin_impl(c, __func__, adapter_id, ids, text_mask, feats, B, Q, k, max_new_tokens, 1.0f, 0, 1.0f, 0, eos_id, pad_id, 0, nullptr,
+                           (hipStream_t)stream);
+}
+
+// HF's finalisation: the best finished hypothesis per item, walked back through the per-step backpointers.  An item not done yet (fewer steps
+// than max_new_tokens were run) first takes its running beams as finished hypotheses of their length, into the same best-k set.
+int opadpo_decode_beam_result(opadpo_ctx* c, int32_t* tokens, float* scores, void* stream) {
+  if (!c) return (int)hipErrorInvalidValue;
+  opadpo_ctx::Decode& D = c->dec;
+  if (!D.active || !D.beams) return cbad(c, __func__, "no active beam decode (call opadpo_decode_beam_begin)");
+  if (!tokens || !scores) return cbad(c, __func__, "null operand");
+  hipStream_t st = (hipStream_t)stream;
+  const int rows = D.B, k = D.beams, items = D.items, T = D.max_new;
+  const BeamState& s = D.bs;
+  std::vector<float> run(rows), fs(rows);
+  std::vector<int32_t> fi(3 * (size_t)rows), fn(items), bp(2 * (size_t)T * rows), step(1);
+  std::vector<uint8_t> dn(items);
+  CK(hipMemcpyAsync(run.data(), s.run_score, rows * sizeof(float), hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(fs.data(), s.fin_score, rows * sizeof(float), hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(fi.data(), s.fin_info, fi.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(fn.data(), s.fin_n, fn.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(bp.data(), s.bp, bp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(dn.data(), s.done, items, hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(step.data(), D.step_d, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  const int last = std::min(step[0], T) - 1;                 // the last step that ran
+  const int32_t* bpar = bp.data();
+  const int32_t* btok = bp.data() + (size_t)T * rows;
+  std::vector<int32_t> out((size_t)items * T, D.pad_id);
+  std::vector<float> best(items, -1.0e9f);
+  for (int b = 0; b < items; ++b) {
+    const int r0 = b * k;
+    std::vector<float> sc(fs.begin() + r0, fs.begin() + r0 + fn[b]);
+    std::vector<int> ist, ipar, itok;
+    for (int q = 0; q < fn[b]; ++q) { ist.push_back(fi[r0 + q]); ipar.push_back(fi[rows + r0 + q]); itok.push_back(fi[2 * rows + r0 + q]); }
+    if (!dn[b] && last >= 0) {
+      for (int q = 0; q < k; ++q) {
+        const float v = run[r0 + q] / (float)(last + 1);
+        size_t p = 0;
+        while (p < sc.size() && sc[p] >= v) ++p;
+        if ((int)p >= k) continue;
+        sc.insert(sc.begin() + p, v); ist.insert(ist.begin() + p, last);
+        ipar.insert(ipar.begin() + p, bpar[(size_t)last * rows + r0 + q]); itok.insert(itok.begin() + p, btok[(size_t)last * rows + r0 + q]);
+        if ((int)sc.size() > k) { sc.pop_back(); ist.pop_back(); ipar.pop_back(); itok.pop_back(); }
+      }
+    }
+    if (sc.empty()) continue;
+    best[b] = sc[0];
+    int t = ist[0], p = ipar[0];
+    out[(size_t)b * T + t] = itok[0];
+    for (int u = t - 1; u >= 0; --u) {
+      out[(size_t)b * T + u] = btok[(size_t)u * rows + p];
+      p = bpar[(size_t)u * rows + p];
+    }
+  }
+  CK(hipMemcpyAsync(tokens, out.data(), out.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(scores, best.data(), best.size() * sizeof(float), hipMemcpyHostToDevice, st));
+  CK(hipStreamSynchronize(st));
   return 0;
 }
 
@@ -1456,8 +1575,9 @@ int opadpo_decode_all_finished(opadpo_ctx* c, int* all_finished, void* stream) {
   if (!c) return (int)hipErrorInvalidValue;
   opadpo_ctx::Decode& D = c->dec;
   if (!D.active || !all_finished) return cbad(c, __func__, "no active rollout");
-  std::vector<uint8_t> f(D.B);
-  CK(hipMemcpyAsync(f.data(), D.finished, D.B, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  const int n = D.beams ? D.items : D.B;
+  std::vector<uint8_t> f(n);
+  CK(hipMemcpyAsync(f.data(), D.finished, n, hipMemcpyDeviceToHost, (hipStream_t)stream));
   CK(hipStreamSynchronize((hipStream_t)stream));
   int all = 1;
   for (uint8_t v : f) all &= (v != 0);
@@ -1472,6 +1592,7 @@ int opadpo_decode_end(opadpo_ctx* c) {
   if (D.graph) { (void)hipGraphDestroy(D.graph); D.graph = nullptr; }
   if (D.cap_stream) { (void)hipStreamSynchronize(D.cap_stream); }
   if (D.active) { ctx_free(c, D.arena, D.bytes); D.arena = nullptr; D.active = false; }
+  D.beams = 0; D.items = 0;
   return 0;
 }
 

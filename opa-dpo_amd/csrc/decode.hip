@@ -24,12 +24,19 @@ namespace {
 // caches and folds that key into its online softmax from registers (the loop skips slot pos, so there is no
 // write -> read dependence through memory inside the launch).  Replaces rope_kv_append + attn_decode: one launch less per
 // layer and step.  Rounding points are those of the two-kernel path (rotated q and k rounded to bf16 before use).
-template <int HD, int NW, bool FUSE = false>
+// BEAM (one BeamDec after the last argument; beam search, FUSE only): row b = blockIdx.y is beam b % k of item b / k.  kc / vc = the items'
+// shared prefix caches [items, nh, Lp, HD] (key_mask [items, Lp]); kc_w / vc_w = the suffix caches [rows, nh, max_new, HD]: the key of suffix
+// slot s = j - Lp of row b lives in physical row table[b][s], and the new token's key is appended at (b, pos - Lp).  The table is
+// double-buffered by the parity of s + 1 for the appended slot s.  The non-beam instantiations (empty pack) are the kernel as it was.
+struct BeamDec { const int32_t* table; long long tstride; int Lp, max_new, k; };
+template <int HD, int NW, bool FUSE = false, typename... BA>
 __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* q, int ldq, const bf16_t* kc, const bf16_t* vc,
                                                                bf16_t* o, const uint8_t* key_mask, int nh, int ctx_arg,
                                                                const int32_t* ctx_ptr, int max_ctx, float scale_log2e, float* ws_part,
                                                                const float* cosb = nullptr, const float* sinb = nullptr,
-                                                               bf16_t* kc_w = nullptr, bf16_t* vc_w = nullptr) {
+                                                               bf16_t* kc_w = nullptr, bf16_t* vc_w = nullptr, BA... beam) {
+  constexpr bool BEAM = sizeof...(BA) > 0;
+  static_assert(!BEAM || FUSE, "the beam form appends the new token: FUSE only");
   constexpr int LPK = HD / 8;            // lanes per key
   constexpr int KPW = 64 / LPK;          // keys per wave step
   constexpr int NG = NW * KPW;           // lane groups (= keys per block step)
@@ -68,6 +75,18 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* q, i
   const bf16_t* kb = kc + seq * HD + d * 8;
   const bf16_t* vb = vc + seq * HD + d * 8;
   const uint8_t* km = key_mask ? key_mask + (size_t)b * max_ctx : nullptr;
+  // beam form: prefix rows of the item, the prefix mask [items, Lp], the row's slot table of this step's parity
+  BeamDec bm{};
+  const bf16_t *kpb = kb, *vpb = vb;
+  const uint8_t* kmb = km;
+  const int32_t* tbl = nullptr;
+  if constexpr (BEAM) {
+    bm = (beam, ...);
+    const size_t pseq = ((size_t)(b / bm.k) * nh + h) * bm.Lp;
+    kpb = kc + pseq * HD + d * 8; vpb = vc + pseq * HD + d * 8;
+    kmb = key_mask ? key_mask + (size_t)(b / bm.k) * bm.Lp : nullptr;
+    tbl = bm.table + (size_t)((pos - bm.Lp + 1) & 1) * bm.tstride + (size_t)b * bm.max_new;
+  }
 
   float m = -1.0e30f, l = 0.f, acc[8];
 #pragma unroll
@@ -78,15 +97,28 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* q, i
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int j = jb + u * NG + g;
-      ok[u] = j < s1 && (!km || km[j]) && j != pos;
+      if constexpr (BEAM) ok[u] = j < s1 && (j >= bm.Lp || !kmb || kmb[j]) && j != pos;      // suffix keys are always visible
+      else ok[u] = j < s1 && (!km || km[j]) && j != pos;
       kk[u] = make_uint4(0, 0, 0, 0);
       vv[u] = make_uint4(0, 0, 0, 0);
       if (j < s1 && j != pos) {          // slots >= ctx are never read (uninitialised memory may hold NaN bit patterns)
         // the KV cache is read exactly once per decode step: non-temporal loads stream it past the L2s (round 4; same-box B = 64: 9.24 -> 8.93 ms
         // per step, B = 8 neutral)
         typedef __attribute__((ext_vector_type(4))) unsigned u4n_t;
+        if constexpr (BEAM) {
+          const bf16_t* kp = kpb + (size_t)j * HD;
+          const bf16_t* vp = vpb + (size_t)j * HD;
+          if (j >= bm.Lp) {
+            const int sl = j - bm.Lp;
+            const size_t r = (((size_t)tbl[sl] * nh + h) * bm.max_new + sl) * HD + d * 8;
+            kp = kc_w + r; vp = vc_w + r;
+          }
+          const u4n_t a = __builtin_nontemporal_load((const u4n_t*)kp), c = __builtin_nontemporal_load((const u4n_t*)vp);
+          kk[u] = make_uint4(a.x, a.y, a.z, a.w); vv[u] = make_uint4(c.x, c.y, c.z, c.w);
+        } else {
         const u4n_t a = __builtin_nontemporal_load((const u4n_t*)(kb + (size_t)j * HD)), c = __builtin_nontemporal_load((const u4n_t*)(vb + (size_t)j * HD));
         kk[u] = make_uint4(a.x, a.y, a.z, a.w); vv[u] = make_uint4(c.x, c.y, c.z, c.w);
+        }
       }
     }
     float sc[U];
@@ -126,14 +158,22 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* q, i
       rope8(krow, kf);
       const uint4 vraw = *(const uint4*)(krow + H + d * 8);
       unpack8(vraw, vf);
+      if constexpr (BEAM) {
+        const size_t wrow = ((size_t)b * nh + h) * bm.max_new + (pos - bm.Lp);
+        *(uint4*)(kc_w + wrow * HD + d * 8) = pack8(kf);
+        *(uint4*)(vc_w + wrow * HD + d * 8) = vraw;
+      } else {
       *(uint4*)(kc_w + (seq + pos) * HD + d * 8) = pack8(kf);
       *(uint4*)(vc_w + (seq + pos) * HD + d * 8) = vraw;
+      }
       float a = 0.f;
 #pragma unroll
       for (int e = 0; e < 8; ++e) a += kf[e] * qf[e];
 #pragma unroll
       for (int off = 1; off < LPK; off <<= 1) a += __shfl_xor(a, off, 64);
-      if (!km || km[pos]) {
+      bool fold = true;                  // beam form: a runtime test too (pos >= Lp), so both forms fold the key through the same branch
+      if constexpr (BEAM) fold = pos >= bm.Lp || !kmb || kmb[pos];
+      if (fold && (BEAM || !km || km[pos])) {
         const float mn = fmaxf(m, a);
         const float alpha = fast_exp2(m - mn), pj = fast_exp2(a - mn);
         m = mn;
@@ -617,6 +657,221 @@ __global__ __launch_bounds__(SAMP_T) void sample_kernel_fast(const float* logits
   }
 }
 
+// ---- beam search (HF GenerationMixin._beam_search, do_sample=False, length_penalty=1, early_stopping=False) ------------------------------
+// Candidates of an item are ranked by the accumulated score log_softmax(logits) + beam score, ties to the LOWER flat index beam * V + token.
+// beam_topk: one workgroup per beam row.  The row goes to LDS once; max and log-sum-exp; a 4-level radix select on the monotone key of the
+// logit finds the 2k-th largest one; the keys above it and the lowest-index ties make the row's 2k candidates (score order = logit order, the
+// shift by -lse + beam score is monotone).  The union of the rows' 2k contains the item's top 2k.  Step 0 (device counter): only beam 0 of an
+// item is live, the others start at -1e9 (as HF); row_div = k reads the item's one prefill row for all its beams.
+constexpr int BEAM_T = 1024, BEAM_W = BEAM_T / 64;
+constexpr float BEAM_NEG = -1.0e9f;
+
+__device__ __forceinline__ float fkey_inv(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+__global__ __launch_bounds__(BEAM_T) void beam_topk_kernel(const float* logits, int ldl, int row_div, int V, int k, const int32_t* step_ptr, int step_arg,
+                                                           const float* run_score, const uint8_t* done, float* cand_val, int32_t* cand_tok) {
+  extern __shared__ __attribute__((aligned(16))) float zr[];        // [V] logits of the row
+  __shared__ uint64_t hist[256];
+  __shared__ float wred[BEAM_W];
+  __shared__ int wcnt[BEAM_W];
+  __shared__ uint32_t s_digit;
+  __shared__ uint64_t s_carry;
+  __shared__ int s_n, s_ties;
+  __shared__ int s_tok[32];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, K2 = 2 * k;
+  if (done[row / k]) return;
+  const int t = step_ptr ? step_ptr[0] : step_arg;
+  const float bs = t == 0 ? (row % k == 0 ? 0.f : BEAM_NEG) : run_score[row];
+  const float* z = logits + (size_t)(row / row_div) * ldl;
+  float mx = -INFINITY;
+  for (int i = tid; i < V; i += BEAM_T) { const float x = z[i]; zr[i] = x; mx = fmaxf(mx, x); }
+  mx = wave_max(mx);
+  if (lane == 0) wred[wave] = mx;
+  __syncthreads();
+  mx = wred[0];
+#pragma unroll
+  for (int i = 1; i < BEAM_W; ++i) mx = fmaxf(mx, wred[i]);
+  float se = 0.f;
+  for (int i = tid; i < V; i += BEAM_T) se += expf(zr[i] - mx);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+  __syncthreads();
+  if (lane == 0) wred[wave] = se;
+  __syncthreads();
+  se = 0.f;
+#pragma unroll
+  for (int i = 0; i < BEAM_W; ++i) se += wred[i];
+  const float ls = logf(se);
+  // radix select: thr = key of the K2-th largest logit, above = number of keys strictly above it
+  uint32_t prefix = 0, pmask = 0;
+  uint64_t above = 0;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();
+    for (int base = 0; base < V; base += BEAM_T) {
+      const int i = base + tid;
+      const uint32_t kk = i < V ? fkey(zr[i]) : 0u;
+      bool mine = i < V && (kk & pmask) == prefix;
+      const uint32_t dg = (kk >> shift) & 255u;
+#pragma unroll 1
+      for (int it = 0; it < 3; ++it) {               // wave-aggregated counting for crowded bins
+        const uint64_t act = __ballot(mine);
+        if (!act) break;
+        const int lead = __ffsll((long long)act) - 1;
+        const uint32_t ldg = __shfl(dg, lead, 64);
+        const uint64_t same = __ballot(mine && dg == ldg);
+        if (lane == lead) atomicAdd((unsigned long long*)&hist[ldg], (unsigned long long)__popcll(same));
+        if (dg == ldg) mine = false;
+      }
+      if (mine) atomicAdd((unsigned long long*)&hist[dg], 1ull);
+    }
+    __syncthreads();
+    if (wave == 0) pick_digit<true>(hist, above, (uint64_t)K2, lane, &s_digit, &s_carry);
+    __syncthreads();
+    prefix |= s_digit << shift;
+    pmask |= 255u << shift;
+    above = s_carry;
+    __syncthreads();
+  }
+  const uint32_t thr = prefix;
+  const int need_ties = K2 - (int)above;           // the lowest-index keys equal to thr fill the rest
+  if (tid == 0) { s_n = 0; s_ties = 0; }
+  __syncthreads();
+  for (int base = 0; base < V; base += BEAM_T) {
+    const int i = base + tid;
+    const uint32_t kk = i < V ? fkey(zr[i]) : 0u;
+    const bool tie = i < V && kk == thr;
+    const uint64_t tm = __ballot(tie);
+    if (lane == 0) wcnt[wave] = __popcll(tm);
+    __syncthreads();
+    int before = s_ties;
+    for (int w = 0; w < wave; ++w) before += wcnt[w];
+    const int rank = before + __popcll(tm & ((1ull << lane) - 1ull));
+    if ((i < V && kk > thr) || (tie && rank < need_ties)) {
+      const int slot = atomicAdd(&s_n, 1);
+      if (slot < K2) s_tok[slot] = i;
+    }
+    __syncthreads();
+    if (tid == 0) { int tot = 0; for (int w = 0; w < BEAM_W; ++w) tot += wcnt[w]; s_ties += tot; }
+    __syncthreads();
+  }
+  if (tid < K2) {
+    const int tok = s_tok[tid];
+    cand_val[(size_t)row * K2 + tid] = ((zr[tok] - mx) - ls) + bs;          // log_softmax as torch rounds it, plus the beam score
+    cand_tok[(size_t)row * K2 + tid] = tok;
+  }
+}
+
+// beam_update: one wave per item.  Merges the k * 2k row candidates into the item's sorted top 2k (64-bit keys: score, then the lower flat
+// index), then applies HF's rules at step t (device counter):
+//   a candidate is finished if its token is EOS or t is the last step; finished ones ranked among the first k enter the item's finished set
+//   (best k by score / (t + 1), generated length with the EOS; ties keep the earlier entry);
+//   the next running beams are the best k unfinished candidates (at the last step the rest, at score - 1e9, keep the rows defined);
+//   the item is done when its finished set is full and best running score / (t + 1) <= its worst finished score (HF's early-stop
+//   heuristic), or at the last step.  A done item is frozen: its beams keep their rows and emit pad.
+// Outputs: cur_tok (the next embedding gather), backpointers bp [2][max_new][rows] (parent row | token), and the slot table rewritten into the
+// other parity buffer: new[i][0..t-1) = old[parent_i][0..t-1), new[i][t-1] = parent_i (the parent appended slot t-1 in its own row).
+// A finished entry is (score, step, parent row, token); no token sequence is copied.
+__global__ __launch_bounds__(64) void beam_update_kernel(const float* cand_val, const int32_t* cand_tok, int k, int V, int rows, int max_new, int eos_id,
+                                                         int pad_id, const int32_t* step_ptr, int step_arg, float* run_score, float* fin_score,
+                                                         int32_t* fin_info, int32_t* fin_n, uint8_t* done, int32_t* cur_tok, int32_t* bp,
+                                                         int32_t* table, long long tstride) {
+  constexpr int E = 8;                              // 64 * 8 >= k * 2k for k <= 16
+  __shared__ int s_par[16];
+  __shared__ float s_fs[16], s_new[16];
+  __shared__ int s_fi[3][16], s_nt[16], s_np[16], s_nf[16];
+  const int item = blockIdx.x, lane = threadIdx.x, K2 = 2 * k, n = k * K2, r0 = item * k;
+  const int t = step_ptr ? step_ptr[0] : step_arg;
+  if (t >= max_new) return;
+  int32_t* bp_par = bp + (size_t)t * rows;
+  int32_t* bp_tok = bp + (size_t)max_new * rows + (size_t)t * rows;
+  const int32_t* told = table + (size_t)(t & 1) * tstride;
+  int32_t* tnew = table + (size_t)((t + 1) & 1) * tstride;
+  const bool frozen = done[item] != 0;
+  if (frozen) {
+    if (lane < k) { cur_tok[r0 + lane] = pad_id; bp_par[r0 + lane] = r0 + lane; bp_tok[r0 + lane] = pad_id; s_par[lane] = r0 + lane; }
+  } else {
+    uint64_t key[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int c = lane + 64 * e;
+      key[e] = 0;
+      if (c < n) {
+        const int r = c / K2;
+        const float v = cand_val[(size_t)(r0 + r) * K2 + c % K2];
+        const uint32_t flat = (uint32_t)r * (uint32_t)V + (uint32_t)cand_tok[(size_t)(r0 + r) * K2 + c % K2];
+        key[e] = ((uint64_t)fkey(v) << 32) | (uint64_t)(0xffffffffu - flat);
+      }
+    }
+    uint64_t mine = 0;                              // lane j < K2: the j-th best candidate
+    for (int j = 0; j < K2; ++j) {
+      uint64_t best = 0;
+#pragma unroll
+      for (int e = 0; e < E; ++e) best = key[e] > best ? key[e] : best;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t other = (uint64_t)__shfl_xor((long long)best, o, 64);
+        best = other > best ? other : best;
+      }
+#pragma unroll
+      for (int e = 0; e < E; ++e) if (key[e] == best) key[e] = 0;
+      if (lane == j) mine = best;
+    }
+    const bool valid = lane < K2;
+    const float val = fkey_inv((uint32_t)(mine >> 32));
+    const uint32_t flat = 0xffffffffu - (uint32_t)(mine & 0xffffffffu);
+    const int par = r0 + (int)(flat / (uint32_t)V), tok = (int)(flat % (uint32_t)V);
+    const bool fin = valid && ((eos_id >= 0 && tok == eos_id) || t == max_new - 1);
+    const uint64_t lt = (1ull << lane) - 1ull;
+    const uint64_t unf = __ballot(valid && !fin), fnd = __ballot(fin);
+    const int n_unf = __popcll(unf);
+    const int slot = fin ? n_unf + __popcll(fnd & lt) : __popcll(unf & lt);
+    if (valid && slot < k) {
+      const int i = r0 + slot;
+      cur_tok[i] = tok; bp_par[i] = par; bp_tok[i] = tok; s_par[slot] = par;
+      run_score[i] = fin ? val + BEAM_NEG : val;
+    }
+    if (lane < k) {                                 // the first k candidates: the ones that may enter the finished set
+      s_new[lane] = val / (float)(t + 1);
+      s_nf[lane] = fin; s_nt[lane] = tok; s_np[lane] = par;
+    }
+    const float run0 = __shfl(fin ? val + BEAM_NEG : val, __ffsll((long long)(n_unf ? unf : fnd)) - 1, 64);
+    if (lane < k) {
+      s_fs[lane] = fin_score[r0 + lane];
+      s_fi[0][lane] = fin_info[r0 + lane]; s_fi[1][lane] = fin_info[rows + r0 + lane]; s_fi[2][lane] = fin_info[2 * rows + r0 + lane];
+    }
+    __syncthreads();
+    if (lane == 0) {
+      int cnt = fin_n[item];
+      for (int j = 0; j < k; ++j) {
+        if (!s_nf[j]) continue;
+        const float sc = s_new[j];
+        int p = 0;
+        while (p < cnt && s_fs[p] >= sc) ++p;
+        if (p >= k) continue;
+        for (int q = min(cnt, k - 1); q > p; --q) { s_fs[q] = s_fs[q - 1]; s_fi[0][q] = s_fi[0][q - 1]; s_fi[1][q] = s_fi[1][q - 1]; s_fi[2][q] = s_fi[2][q - 1]; }
+        s_fs[p] = sc; s_fi[0][p] = t; s_fi[1][p] = s_np[j]; s_fi[2][p] = s_nt[j];
+        cnt = min(cnt + 1, k);
+      }
+      fin_n[item] = cnt;
+      const bool full = cnt == k;
+      if (t == max_new - 1 || (full && !(run0 / (float)(t + 1) > s_fs[k - 1]))) done[item] = 1;
+    }
+    __syncthreads();
+    if (lane < k) {
+      fin_score[r0 + lane] = s_fs[lane];
+      fin_info[r0 + lane] = s_fi[0][lane]; fin_info[rows + r0 + lane] = s_fi[1][lane]; fin_info[2 * rows + r0 + lane] = s_fi[2][lane];
+    }
+  }
+  __syncthreads();
+  if (t >= 1) {
+    for (int idx = lane; idx < k * t; idx += 64) {
+      const int q = idx / t, s = idx - q * t, p = s_par[q];
+      tnew[(size_t)(r0 + q) * max_new + s] = s == t - 1 ? p : told[(size_t)p * max_new + s];
+    }
+  }
+}
+
 }  // namespace
 
 static int attn_decode_splits(int B, int nh, int max_ctx) {
@@ -659,6 +914,46 @@ hipError_t launch_attn_decode_fused(const bf16_t* qkv, int ld, const float* cosb
   else           { if (fat) ADF(64, 16); else ADF(64, 4); }
 #undef ADF
   if (splits > 1) hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(B * nh), dim3(hd), 0, st, part, o, splits, hd);
+  return hipGetLastError();
+}
+
+hipError_t launch_attn_decode_beam(const bf16_t* qkv, int ld, const float* cosb, const float* sinb, const bf16_t* kp, const bf16_t* vp, bf16_t* ks,
+                                   bf16_t* vs, bf16_t* o, const uint8_t* prefix_mask, int items, int k, int nh, int hd, const int32_t* pos_ptr, int Lp,
+                                   int max_new, const int32_t* table, long long table_stride, float scale, void* workspace, size_t workspace_bytes,
+                                   hipStream_t st) {
+  const int rows = items * k, max_ctx = Lp + max_new;
+  if (rows <= 0) return hipSuccess;
+  if ((hd != 64 && hd != 128) || !pos_ptr || !table || ld % 8 || k <= 0) return hipErrorInvalidValue;
+  int splits = attn_decode_splits(rows, nh, max_ctx);
+  if (splits > 1 && (!workspace || workspace_bytes < attn_decode_workspace_bytes(rows, nh, hd, max_ctx))) splits = 1;
+  float* part = (float*)workspace;
+  const float sl2 = scale * 1.4426950408889634f;
+  const bool fat = attn_decode_fat(rows, nh, splits);
+  const dim3 gr(nh, rows, splits);
+  const BeamDec bm{table, table_stride, Lp, max_new, k};
+#define ADB(HD_, NW_) hipLaunchKernelGGL((attn_decode_kernel<HD_, NW_, true, BeamDec>), gr, dim3(NW_ * 64), 0, st, qkv, ld, kp, vp, o, prefix_mask, nh, 0, pos_ptr, \
+                                         max_ctx, sl2, part, cosb, sinb, ks, vs, bm)
+  if (hd == 128) { if (fat) ADB(128, 16); else ADB(128, 4); }
+  else           { if (fat) ADB(64, 16); else ADB(64, 4); }
+#undef ADB
+  if (splits > 1) hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(rows * nh), dim3(hd), 0, st, part, o, splits, hd);
+  return hipGetLastError();
+}
+
+hipError_t launch_beam_step(const float* logits, int ldl, int row_div, int items, int k, int V, int max_new, int eos_id, int pad_id,
+                            const int32_t* step_ptr, int step, BeamState s, hipStream_t st) {
+  if (items <= 0) return hipSuccess;
+  if (k <= 0 || k > OPADPO_MAX_BEAMS || 2 * k > V || V > SAMP_MAXV || items * k > 64) return hipErrorInvalidValue;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)beam_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SAMP_MAXV * 4);
+    attr_set = true;
+  }
+  const int rows = items * k;
+  hipLaunchKernelGGL(beam_topk_kernel, dim3(rows), dim3(BEAM_T), (size_t)V * 4, st, logits, ldl, row_div, V, k, step_ptr, step, s.run_score, s.done,
+                     s.cand_val, s.cand_tok);
+  hipLaunchKernelGGL(beam_update_kernel, dim3(items), dim3(64), 0, st, s.cand_val, s.cand_tok, k, V, rows, max_new, eos_id, pad_id, step_ptr, step,
+                     s.run_score, s.fin_score, s.fin_info, s.fin_n, s.done, s.cur_tok, s.bp, s.table, s.table_stride);
   return hipGetLastError();
 }
 

@@ -215,3 +215,17 @@ hipError_t launch_attn_decode_fused(const bf16_t* qkv, int ld, const float* cosb
                                     void* workspace, size_t workspace_bytes, hipStream_t st);
 hipError_t launch_rope_kv_append(bf16_t* qkv, int ld, const float* cosb, const float* sinb, bf16_t* kc, bf16_t* vc, int B, int nh,
                                  int hd, const int32_t* pos_ptr, int max_ctx, hipStream_t st);
+// beam search (decode.hip): the fused decode attention over a shared prefix cache [items, nh, Lp, hd] and per-row suffix caches
+// [items*k, nh, max_new, hd] addressed through the slot table (two parity buffers table_stride elements apart; 0 = one buffer)
+hipError_t launch_attn_decode_beam(const bf16_t* qkv, int ld, const float* cosb, const float* sinb, const bf16_t* kp, const bf16_t* vp, bf16_t* ks,
+                                   bf16_t* vs, bf16_t* o, const uint8_t* prefix_mask, int items, int k, int nh, int hd, const int32_t* pos_ptr, int Lp,
+                                   int max_new, const int32_t* table, long long table_stride, float scale, void* workspace, size_t workspace_bytes,
+                                   hipStream_t st);
+// device state of a beam search over items x k rows (rows = items * k; include/opadpo_hip.h opadpo_beam_step lists the shapes)
+struct BeamState {
+  float* run_score; float* cand_val; int32_t* cand_tok; float* fin_score; int32_t* fin_info; int32_t* fin_n; uint8_t* done;
+  int32_t* cur_tok; int32_t* bp; int32_t* table; long long table_stride;
+};
+// beam_topk + beam_update for step step_ptr[0] (or `step`): logits row of beam row i = i / row_div
+hipError_t launch_beam_step(const float* logits, int ldl, int row_div, int items, int k, int V, int max_new, int eos_id, int pad_id,
+                            const int32_t* step_ptr, int step, BeamState s, hipStream_t st);

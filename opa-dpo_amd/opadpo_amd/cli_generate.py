@@ -155,6 +155,10 @@ def main_rollout(argv: Optional[List[str]] = None) -> None:
 def main_eval(argv: Optional[List[str]] = None) -> None:
     from .eval_generate import answer_questions, question_chunk
     ns, _ignored = eval_parser().parse_known_args(sys.argv[1:] if argv is None else argv)
+    if ns.num_beams < 1:
+        raise SystemExit(f"--num_beams must be >= 1 (got {ns.num_beams})")
+    if ns.num_beams > 1 and ns.temperature and ns.temperature > 0:
+        raise SystemExit(f"beam sampling is not supported: --num_beams {ns.num_beams} needs --temperature 0 (got {ns.temperature})")
     if os.path.exists(ns.answers_file):
         print(f"{ns.answers_file} already exists. Please delete it first.")
         raise SystemExit(1)
@@ -164,7 +168,8 @@ def main_eval(argv: Optional[List[str]] = None) -> None:
     n = answer_questions(engine, tok, questions, ns.image_folder, os.path.expanduser(ns.answers_file), adapter=adapter,
                          model_id=os.path.basename(os.path.normpath(ns.model_path)), temperature=ns.temperature, top_p=ns.top_p,
                          short_eval=ns.short_eval, test_prompt=ns.test_prompt, image_size=engine.d.image_size,
-                         pad_to_square=ns.image_aspect_ratio == "pad", merge_adapter=ns.merge_adapter, batch_size=ns.batch_size)
+                         pad_to_square=ns.image_aspect_ratio == "pad", merge_adapter=ns.merge_adapter, batch_size=ns.batch_size,
+                         num_beams=ns.num_beams)
     print(f"{n} answers -> {ns.answers_file}")
 
 

@@ -296,3 +296,38 @@ class CtxEngine(LlavaEngine):
         finally:
             self._call("opadpo_decode_end")
         return history.t().contiguous().to(torch.int64)
+
+    @torch.no_grad()
+    def generate_beams(self, adapter, queries: torch.Tensor, query_attn_masks: torch.Tensor, image_feats: torch.Tensor, *, num_beams: int,
+                       max_new_tokens: int, eos_token_id: int, pad_token_id: int, use_graph: bool):
+        """Beam search (HF generate(num_beams=k, do_sample=False, length_penalty=1.0, early_stopping=False)) -> (tokens [B, max_new_tokens]
+        int64 with EOS kept and pad after it, scores [B] fp32 = sum of token log-probabilities / generated length).  One prefill per query;
+        selection, backpointers and the KV slot table stay on the device (opadpo_decode_beam_begin / opadpo_decode_run / _beam_result)."""
+        dev, d = self.dev, self.d
+        B, Q = queries.shape
+        k = int(num_beams)
+        self._ensure_rope(Q + d.n_patches - 1 + max_new_tokens)
+        slot = self.adapter_slot(adapter)
+        ids = queries.to(dev).to(torch.int32).contiguous()
+        tmask = query_attn_masks.to(dev).to(torch.uint8).contiguous()
+        feats = image_feats.contiguous()
+        tokens = torch.empty(B, max_new_tokens, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, dtype=torch.float32, device=dev)
+        st = L.stream()
+        self._call("opadpo_decode_beam_begin", slot, _ptr(ids), _ptr(tmask), _ptr(feats), B, Q, k, int(max_new_tokens), int(eos_token_id),
+                   int(pad_token_id), st)
+        try:
+            left = max_new_tokens - 1
+            fin = C.c_int(0)
+            while left > 0:
+                n = min(32, left)
+                self._call("opadpo_decode_run", n, int(use_graph), st)
+                left -= n
+                if left > 0:
+                    self._call("opadpo_decode_all_finished", C.byref(fin), st)
+                    if fin.value:
+                        break
+            self._call("opadpo_decode_beam_result", _ptr(tokens), _ptr(scores), st)
+        finally:
+            self._call("opadpo_decode_end")
+        return tokens.to(torch.int64), scores

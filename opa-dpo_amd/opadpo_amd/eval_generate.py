@@ -29,13 +29,18 @@ def adapter_dir_of(checkpoint: str) -> str:
 def generate_from_checkpoint(engine: LlavaEngine, checkpoint: Optional[str], queries: torch.Tensor, query_attn_masks: torch.Tensor,
                              images: torch.Tensor, *, max_new_tokens: int = 64, temperature: float = 0.0, top_p: float = 1.0,
                              top_k: int = 0, seed: int = 0, adapter: Optional[LoraAdapter] = None,
-                             merge_adapter: bool = False) -> torch.Tensor:
+                             merge_adapter: bool = False, num_beams: int = 1) -> torch.Tensor:
     """-> [B, max_new_tokens] int64, pad after EOS.  temperature == 0 -> greedy (the reference passes do_sample=False then).
-    merge_adapter: fold the (frozen) adapter into its own copy of the projections first (generate.Generator)."""
+    merge_adapter: fold the (frozen) adapter into its own copy of the projections first (generate.Generator).
+    num_beams > 1: beam search (model.generate(num_beams=..., do_sample=False)); beam sampling (temperature > 0) is refused."""
+    if num_beams > 1 and temperature and temperature > 0:
+        raise ValueError(f"beam sampling is not supported: num_beams={num_beams} needs temperature 0 (got {temperature})")
     if adapter is None and checkpoint is not None:
         adapter = LoraAdapter(engine.d, load_adapter(adapter_dir_of(checkpoint)), engine.dev, trainable=False)
     gen = Generator(engine, adapter, merge_adapter=merge_adapter)
-    if temperature and temperature > 0:
+    if num_beams > 1:
+        out = gen.generate(queries, query_attn_masks, images, max_new_tokens=max_new_tokens, num_beams=num_beams)
+    elif temperature and temperature > 0:
         out = gen.generate(queries, query_attn_masks, images, max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k,
                            top_p=top_p, seed=seed)
     else:
@@ -64,7 +69,7 @@ def answer_questions(engine: LlavaEngine, tokenizer, questions: list, image_fold
                      checkpoint: Optional[str] = None, adapter: Optional[LoraAdapter] = None, model_id: str = "opadpo-hip",
                      temperature: float = 0.0, top_p: Optional[float] = None, short_eval: bool = False, max_new_tokens: Optional[int] = None,
                      test_prompt: Optional[str] = DEFAULT_TEST_PROMPT, image_size: int = 336, pad_to_square: bool = True, seed: int = 0,
-                     merge_adapter: bool = False, batch_size: int = 1) -> int:
+                     merge_adapter: bool = False, batch_size: int = 1, num_beams: int = 1) -> int:
     """One JSON line per question: question_id, prompt (the bare question), text (stripped answer, a trailing '</s>' removed),
     answer_id, model_id, metadata (model_vqa.py:143-262).  Refuses to overwrite an existing answers file like the script's
     __main__.  max_new_tokens defaults to 64 (`short_eval`) or 1024.  merge_adapter: merge the frozen checkpoint adapter once (PEFT
@@ -98,7 +103,7 @@ def answer_questions(engine: LlavaEngine, tokenizer, questions: list, image_fold
                                   for line in chunk]).to(engine.dev)
             out = generate_from_checkpoint(engine, None, ids.to(engine.dev), mask.to(engine.dev), images, max_new_tokens=n_new,
                                            temperature=temperature, top_p=1.0 if top_p is None else top_p, seed=seed + n, adapter=adapter,
-                                           merge_adapter=merge_adapter)
+                                           merge_adapter=merge_adapter, num_beams=num_beams)
             for line, text in zip(chunk, tokenizer.batch_decode(out.cpu(), skip_special_tokens=True)):
                 text = text.strip()
                 if text.endswith(SEP2):

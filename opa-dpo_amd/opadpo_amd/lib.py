@@ -67,6 +67,8 @@ SIGNATURES = {
     "opadpo_rope_kv_append": [_p, _i, _p, _p, _p, _p, _i, _i, _i, _p, _i, _p],
     "opadpo_attn_decode_fused": [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _f, _p, _sz, _p],
     "opadpo_sample": [_p, _i, _i, _i, _f, _i, _f, _u64, _u64, _p, _p, _i, _i, _p, _p, _p],
+    "opadpo_attn_decode_beam": [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _f, _p, _sz, _p],
+    "opadpo_beam_step": [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
 }
 # context API (include/opadpo_hip.h, "Context API"): sequence-level entry points on an opaque opadpo_ctx*
 SIGNATURES.update({
@@ -91,6 +93,8 @@ SIGNATURES.update({
     "opadpo_decode_run": [_p, _i, _i, _p],
     "opadpo_decode_all_finished": [_p, _p, _p],
     "opadpo_decode_end": [_p],
+    "opadpo_decode_beam_begin": [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
+    "opadpo_decode_beam_result": [_p, _p, _p, _p],
     "opadpo_allreduce_grads": [_p, _p, _sz, _i, _p],
     "opadpo_reduce_scatter_grads": [_p, _p, _p, _sz, _i, _p],
     "opadpo_all_gather_params": [_p, _p, _p, _sz, _i, _p],
