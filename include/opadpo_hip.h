@@ -177,6 +177,16 @@ int opadpo_rope(uint16_t* qk, int ld, const float* cos_tab, const float* sin_tab
                 int inverse, const int32_t* pos_base, int seg_prefix, int seg_len, void* stream);
 int opadpo_silu_mul_fwd(const uint16_t* gu, uint16_t* act, int rows, int F, void* stream);   /* gu = [gate | up] */
 int opadpo_silu_mul_bwd(const uint16_t* dact, const uint16_t* gu, uint16_t* dgu, int rows, int F, void* stream);
+/* LoRA dropout (PEFT lora.Linear: the LoRA branch reads dropout(x)).  The keep mask is a pure function, never stored:
+ *   keep(seed, call, layer, module, row, col) = philox4x32_10(counter, key)[col & 3] >= floor(p * 2^32)      (unsigned compare)
+ *   counter = (col >> 2, row, call & 0xffffffff, call >> 32), key = (seed, layer * 8 + module); seed < 2^32, 0 <= p < 1, module 0..6 = q k v o gate up down.
+ * opadpo_lora_dropout_fwd: out [rows, g*K] = g masked copies of x [rows, K] side by side for modules module0 .. module0 + g - 1 (module0 + g <= 7, K % 8 == 0);
+ * a kept element is bf16(x * fp32(1 / (1 - p))) (one rounding), a dropped one 0.  row_idx (nullable, int32 [rows]): the row number every row hashes with
+ * (default: its index).  opadpo_lora_dropout_bwd_add: dx [rows, K] += sum_j keep_j * u[:, j*K : (j+1)*K] * fp32(1 / (1 - p)), fp32 sum in module order. */
+int opadpo_lora_dropout_fwd(const uint16_t* x, uint16_t* out, int rows, int K, int g, double p, uint64_t seed, uint64_t call, int layer, int module0,
+                            const int32_t* row_idx, void* stream);
+int opadpo_lora_dropout_bwd_add(uint16_t* dx, const uint16_t* u, int rows, int K, int g, double p, uint64_t seed, uint64_t call, int layer, int module0,
+                                const int32_t* row_idx, void* stream);
 
 /* ---- embedding gather + multimodal splice (LLaVA prepare_inputs_labels_for_multimodal) ------------
  * ids/text_mask [S,n_txt]; each row holds exactly one image_token, replaced by the P rows
@@ -419,6 +429,12 @@ int opadpo_seq_logprobs_fwd(opadpo_ctx* ctx, int adapter_id, const int32_t* ids,
  * the image features (OPA LoRA-SFT stage), written when layer_lo == 0. */
 int opadpo_seq_logprobs_bwd(opadpo_ctx* ctx, opadpo_saved* saved, const float* dlogp, const float* dent, float* d_feats, int layer_hi,
                             int layer_lo, void* stream);
+/* LoRA dropout of the NEXT training forward (opadpo_seq_logprobs_fwd with train = 1) of this context: rate p in [0, 1), seed < 2^32 and the host's
+ * per-training-forward counter `call` (different for every micro-batch and rank).  The forward consumes the setting (the one after it runs without dropout
+ * unless this is called again) and records it in the saved handle: opadpo_seq_logprobs_bwd regenerates the same masks.  One mask per adapted Linear (7 per
+ * decoder layer), hashed with the pass's own row numbers; no-grad passes (train = 0), merged adapters, prefill and decode never apply dropout.  p = 0 is
+ * the pass without this call: the same launches, buffers and bits. */
+int opadpo_ctx_set_lora_dropout(opadpo_ctx* ctx, double p, uint64_t seed, uint64_t call);
 int opadpo_saved_release(opadpo_ctx* ctx, opadpo_saved* saved);
 /* diagnostics (parity tests: the per-layer drift curve of the residual stream): copies the fp32 residual stream ENTERING decoder
  * layer `layer` of a training forward, [rows, hidden], into dst (device memory, rows*hidden floats) and returns the row count in

@@ -319,6 +319,22 @@ int opadpo_silu_mul_fwd(const uint16_t* gu, uint16_t* act, int rows, int F, void
 int opadpo_silu_mul_bwd(const uint16_t* dact, const uint16_t* gu, uint16_t* dgu, int rows, int F, void* stream) {
   return done(launch_silu_mul_bwd(dact, gu, dgu, rows, F, S(stream)), "opadpo_silu_mul_bwd");
 }
+int opadpo_lora_dropout_fwd(const uint16_t* x, uint16_t* out, int rows, int K, int g, double p, uint64_t seed, uint64_t call, int layer, int module0,
+                            const int32_t* row_idx, void* stream) {
+  LoraDropout dp;
+  if (lora_dropout_make(p, seed, call, &dp)) return bad("opadpo_lora_dropout_fwd", "need 0 <= p < 1 and seed < 2^32");
+  if (!x || !out || rows < 0 || K <= 0 || K % 8) return bad("opadpo_lora_dropout_fwd", "null operand, or K not a positive multiple of 8");
+  if (g < 1 || module0 < 0 || module0 + g > 7 || layer < 0) return bad("opadpo_lora_dropout_fwd", "modules outside 0..6 or negative layer");
+  return done(launch_lora_dropout_fwd(x, out, rows, K, g, dp, layer, module0, row_idx, S(stream)), "opadpo_lora_dropout_fwd");
+}
+int opadpo_lora_dropout_bwd_add(uint16_t* dx, const uint16_t* u, int rows, int K, int g, double p, uint64_t seed, uint64_t call, int layer, int module0,
+                                const int32_t* row_idx, void* stream) {
+  LoraDropout dp;
+  if (lora_dropout_make(p, seed, call, &dp)) return bad("opadpo_lora_dropout_bwd_add", "need 0 <= p < 1 and seed < 2^32");
+  if (!dx || !u || rows < 0 || K <= 0 || K % 8) return bad("opadpo_lora_dropout_bwd_add", "null operand, or K not a positive multiple of 8");
+  if (g < 1 || module0 < 0 || module0 + g > 7 || layer < 0) return bad("opadpo_lora_dropout_bwd_add", "modules outside 0..6 or negative layer");
+  return done(launch_lora_dropout_bwd_add(dx, u, rows, K, g, dp, layer, module0, row_idx, S(stream)), "opadpo_lora_dropout_bwd_add");
+}
 int opadpo_embed_splice(const int32_t* ids, const uint8_t* text_mask, const uint16_t* embed, const uint16_t* feats,
                         const int32_t* feat_row, const uint8_t* image_mask, void* x, int x_f32, uint8_t* key_mask,
                         int S_, int n_txt, int P, int H, int image_token, void* stream) {

@@ -216,6 +216,9 @@ struct opadpo_saved {
   // ragged rows (padding removed): M = valid rows of the batch, L = longest sequence; meta / row_pos live in the arena
   int ragged = 0, meta_stride = 0, S_pad_rows = 0;
   int32_t *meta = nullptr, *row_pos = nullptr;
+  // LoRA dropout of this pass (opadpo_ctx_set_lora_dropout; training passes only): the masks are regenerated from `drop` in the backward; xm = scratch of
+  // the masked copies of one Linear's input, [M, max(3 hidden, ffn)]
+  int drop_on = 0; LoraDropout drop{}; bf16_t* xm = nullptr;
 };
 
 struct opadpo_ctx {
@@ -246,6 +249,7 @@ struct opadpo_ctx {
   size_t arena_hint[2][16] = {};                  // largest activation arena requested so far, per (no-grad / training pass, responses per row K):
                                                   // CoPO's K = 2 masked pass does not inherit the K = 3 pass's worst case
   std::vector<opadpo_saved*> live;
+  bool next_drop_on = false; LoraDropout next_drop{};      // opadpo_ctx_set_lora_dropout: consumed by the next training forward
   // dispatch: opadpo_ctx_set_flags(gemm_variant, use_tr), parsed once; the use_tr bits below are off for a negative word
   KernelOverrides kernel;                         // gemm_variant, bits 0, 3 and 8 over the process flags (resolve_flags, per launch)
   bool streaming_dec_gemm = false;                // bit 5: decode steps of 9..64 sequences keep the 8/16-row streaming GEMMs
@@ -399,6 +403,8 @@ LoraOff lora_off(const opadpo_dims& d) {
   return o;
 }
 
+inline bool lw_kind1(const opadpo_ctx::Adapter& ad) { return ad.kind == 1; }
+
 hipError_t ensure_rope(opadpo_ctx* c, int len, hipStream_t st) {
   if (c->cosb && c->rope_len >= len) return hipSuccess;
   if (c->cosb && !c->rope_own) return hipErrorInvalidValue;      // caller-provided tables are too short
@@ -428,6 +434,9 @@ hipError_t ensure_rope(opadpo_ctx* c, int len, hipStream_t st) {
 
 // ---- one Llama decoder layer over M = S*Lp rows (model.py layer_fwd / mlp_fwd) ------------------------------------------------
 struct LayerBufs { bf16_t *n1, *qkv, *t_qkv, *attn, *t_o, *n2, *t_gu, *gu, *act, *t_d; float *rstd1, *rstd2, *lse, *h; };
+// LoRA dropout of a training forward (nullptr = off: the launches below are the ones without it): every A product reads masked copies of its input
+// from xm instead of the input - q|k|v and gate|up one copy per module side by side, selected per r-wide column group (grouped A1)
+struct DropFwd { LoraDropout dp; bf16_t* xm; };
 
 // ydef != nullptr ("deferred residual", the full-sequence passes): the down projection writes its fp32 product to ydef WITHOUT the
 // residual - the RMSNorm that follows adds it (rmsnorm_sum_fwd: x = h + y in the same fp32 arithmetic, so h / x keep their bits).
@@ -437,7 +446,7 @@ struct LayerBufs { bf16_t *n1, *qkv, *t_qkv, *attn, *t_o, *n2, *t_gu, *gu, *act,
 // GEMM whatever K, profiles/r05m_resid_probe_k.txt), so the add lives in the projections again and this form is the A/B switch (context flag bit 13).
 // ydef == nullptr (decode steps: a few rows; fused-residual full-sequence passes): residual in the epilogue, result in xo.
 hipError_t mlp_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const float* h, float* xo, const LayerBufs& b, int M, int stream_hint, hipStream_t st,
-                   float* ydef = nullptr, bool norm_done = false) {
+                   float* ydef = nullptr, bool norm_done = false, const DropFwd* dr = nullptr, const int32_t* drop_rows = nullptr) {
   const opadpo_dims& d = c->d;
   const int H = d.hidden, F = d.ffn, r = d.lora_r;
   const float s = d.lora_alpha / d.lora_r;
@@ -451,6 +460,10 @@ hipError_t mlp_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const fl
   bool have_gu = true;
   if (lw) {
     GemmNTArgs g1_ = gemm(b.n2, H, lw + o.a_gu, H, H, b.t_gu, 2 * r, 0, M, 2 * r); g1_.alpha = s; g1_.act |= stream_hint;
+    if (dr) {                                       // gate, up: modules 4, 5
+      if ((e = launch_lora_dropout_fwd(b.n2, dr->xm, M, H, 2, dr->dp, i, 4, drop_rows, st)) != hipSuccess) return e;
+      g1_.A1 = dr->xm; g1_.lda1 = 2 * H; g1_.a1_group_n = r; g1_.a1_group_stride = H;
+    }
     if ((e = run_gemm(c, g1_, st)) != hipSuccess) return e;
     GemmNTArgs g2 = gemm(b.n2, H, w.wgu, H, H, b.gu, 2 * F, 0, M, 2 * F); tail(g2, b.t_gu, 2 * r, lw + o.b_gu, r, r, F, r); g2.act |= stream_hint;
     if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
@@ -465,6 +478,10 @@ hipError_t mlp_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const fl
   if (have_gu && (e = launch_silu_mul_fwd(b.gu, b.act, M, F, st)) != hipSuccess) return e;
   if (lw) {
     GemmNTArgs g3 = gemm(b.act, F, lw + o.a_d, F, F, b.t_d, r, 0, M, r); g3.alpha = s; g3.act |= stream_hint;
+    if (dr) {                                       // down: module 6
+      if ((e = launch_lora_dropout_fwd(b.act, dr->xm, M, F, 1, dr->dp, i, 6, drop_rows, st)) != hipSuccess) return e;
+      g3.A1 = dr->xm;
+    }
     if ((e = run_gemm(c, g3, st)) != hipSuccess) return e;
     GemmNTArgs g4 = gemm(b.act, F, w.wd, F, F, ydef ? ydef : xo, H, 1, M, H); tail(g4, b.t_d, r, lw + o.b_d, r, r); g4.act |= stream_hint;
     if (!ydef) resid(g4, h, H, 1);
@@ -484,9 +501,10 @@ struct TopRows { const int32_t* urow; int n; bf16_t* attn_u; float* x_u; };
 // the caller hands (b.h, Y) to the next layer / the final norm.
 hipError_t layer_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const float* res, const float* yin, float* x, float* Y, const LayerBufs& b, int S, int Lp,
                      const uint8_t* key_mask, int seg0, int seg1, bf16_t* kc, bf16_t* vc, int max_ctx, hipStream_t st, const Rag* rg = nullptr,
-                     const TopRows* top = nullptr) {
+                     const TopRows* top = nullptr, const DropFwd* dr = nullptr) {
   const opadpo_dims& d = c->d;
   const int H = d.hidden, r = d.lora_r, nh = d.n_heads, hd = d.head_dim;
+  if (dr && !lw_kind1(ad)) dr = nullptr;            // dropout belongs to the LoRA branch
   const int M = rg ? rg->rows : S * Lp;
   const float s = d.lora_alpha / d.lora_r;
   const opadpo_layer_weights& w0 = c->layers[i];
@@ -506,6 +524,10 @@ hipError_t layer_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const 
   auto with_rope = [&](GemmNTArgs& g) { if (fuse_rope) { g.rope_pos = rg->row_pos; g.rope_l2theta = log2f(d.rope_theta); g.rope_cols = 2 * H; } };
   if (lw) {
     GemmNTArgs g1_ = gemm(b.n1, H, lw + o.a_qkv, H, H, b.t_qkv, 3 * r, 0, M, 3 * r); g1_.alpha = s;
+    if (dr) {                                       // q, k, v: modules 0..2, three masks over the same n1
+      if ((e = launch_lora_dropout_fwd(b.n1, dr->xm, M, H, 3, dr->dp, i, 0, nullptr, st)) != hipSuccess) return e;
+      g1_.A1 = dr->xm; g1_.lda1 = 3 * H; g1_.a1_group_n = r; g1_.a1_group_stride = H;
+    }
     if ((e = run_gemm(c, g1_, st)) != hipSuccess) return e;
     GemmNTArgs g2 = gemm(b.n1, H, w.wqkv, H, H, b.qkv, 3 * H, 0, M, 3 * H); tail(g2, b.t_qkv, 3 * r, lw + o.b_qkv, r, r, H, r);
     with_rope(g2);
@@ -548,6 +570,10 @@ hipError_t layer_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const 
   float* const o_dst = fr ? b.h : Y;
   if (lw) {
     GemmNTArgs g3 = gemm(attn, H, lw + o.a_o, H, H, b.t_o, r, 0, Mo, r); g3.alpha = s;
+    if (dr) {                                       // o: module 3; compact top layer: the rows hash with their row of the pass (urow), not their index in U
+      if ((e = launch_lora_dropout_fwd(attn, dr->xm, Mo, H, 1, dr->dp, i, 3, top ? top->urow : nullptr, st)) != hipSuccess) return e;
+      g3.A1 = dr->xm;
+    }
     if ((e = run_gemm(c, g3, st)) != hipSuccess) return e;
     GemmNTArgs g4 = gemm(attn, H, w.wo, H, H, o_dst, H, 1, Mo, H); tail(g4, b.t_o, r, lw + o.b_o, r, r);
     if (fr) resid(g4, xr, H, 1);
@@ -559,10 +585,10 @@ hipError_t layer_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const 
   }
   if (fr) {
     if ((e = launch_rmsnorm_fwd(b.h, 1, w0.ln2, b.n2, b.rstd2, Mo, H, d.rms_eps, st)) != hipSuccess) return e;      // n2 = norm(h)
-    return mlp_fwd(c, i, ad, b.h, Y, b, Mo, 0, st, nullptr, true);                                                   // Y = h + down(..)
+    return mlp_fwd(c, i, ad, b.h, Y, b, Mo, 0, st, nullptr, true, dr, top ? top->urow : nullptr);                   // Y = h + down(..)
   }
   if ((e = launch_rmsnorm_sum_fwd(xr, 1, Y, 1, (size_t)Mo * H, w0.ln2, b.h, b.n2, b.rstd2, Mo, H, d.rms_eps, st)) != hipSuccess) return e;      // h = x + attn . Wo, n2 = norm(h)
-  return mlp_fwd(c, i, ad, b.h, nullptr, b, Mo, 0, st, Y, true);
+  return mlp_fwd(c, i, ad, b.h, nullptr, b, Mo, 0, st, Y, true, dr, top ? top->urow : nullptr);
 }
 
 size_t saved_layout(const opadpo_dims& d, opadpo_saved* sv, void* base) {
@@ -600,6 +626,7 @@ size_t saved_layout(const opadpo_dims& d, opadpo_saved* sv, void* base) {
   sv->attn_u = cv.take<bf16_t>(sv->ragged ? std::min(R, M) * H : 1);
   sv->meta = cv.take<int32_t>(sv->ragged ? (size_t)sv->S * sv->meta_stride : 1);
   sv->row_pos = cv.take<int32_t>(sv->ragged ? M : 1);
+  sv->xm = cv.take<bf16_t>(sv->drop_on ? M * std::max(3 * H, F) : 0);      // nothing without dropout: the arena of such a pass keeps its size
   return cv.off;
 }
 
@@ -680,6 +707,14 @@ int opadpo_ctx_set_flags(opadpo_ctx* c, int gemm_variant, int use_tr) {
   c->wgrad_atomic = bit(12);
   c->resid_deferred = bit(13);
   c->swiglu_bwd_own_kernel = bit(14);
+  return 0;
+}
+
+int opadpo_ctx_set_lora_dropout(opadpo_ctx* c, double p, uint64_t seed, uint64_t call) {
+  if (!c) return (int)hipErrorInvalidValue;
+  LoraDropout dp;
+  if (lora_dropout_make(p, seed, call, &dp)) return cbad(c, __func__, "need 0 <= p < 1 and seed < 2^32");
+  c->next_drop = dp; c->next_drop_on = true;
   return 0;
 }
 
@@ -847,6 +882,10 @@ int opadpo_seq_logprobs_fwd(opadpo_ctx* c, int adapter_id, const int32_t* ids, c
   const int pfx = Lp - K * T;
   sv->seg_prefix = K > 1 ? pfx : 0; sv->seg_len = K > 1 ? T : 0;
   sv->ids = ids; sv->feat_row = feat_row;
+  if (train) {                                      // the dropout setting belongs to ONE training forward; rate 0 is the pass without it
+    if (c->next_drop_on && c->next_drop.thr > 0) { sv->drop_on = 1; sv->drop = c->next_drop; }
+    c->next_drop_on = false;
+  }
   // ragged rows: row_plan (HOST, [S][K+1]) = per sequence the number of dropped left-pad positions and the valid length of every
   // response (trailing pad dropped); the valid rows of the batch become the M of every row-wise kernel of the pass
   std::vector<int32_t> metav;
@@ -946,6 +985,7 @@ int opadpo_seq_logprobs_fwd(opadpo_ctx* c, int adapter_id, const int32_t* ids, c
   const float* yin = nullptr;
   const TopRows top{sv->urow, sv->Uc, sv->attn_u, sv->hs};                 // hs is free until the head (and |U| <= R rows fit)
   const bool fr = !c->resid_deferred;
+  const DropFwd drop_fwd{sv->drop, sv->xm};
   for (int i = 0; i < d.n_layers; ++i) {
     const LayerBufs lb = slot(d, sv, train ? i : 0);
     float* x = sv->x + (size_t)(train ? i : (i & 1)) * MH;
@@ -953,7 +993,7 @@ int opadpo_seq_logprobs_fwd(opadpo_ctx* c, int adapter_id, const int32_t* ids, c
     // old branch-product slot; no-grad: the other of the two alternating slots)
     float* const xo = fr ? sv->x + (size_t)(train ? i + 1 : ((i + 1) & 1)) * MH : Y;
     CKS(layer_fwd(c, i, ad, res, yin, x, xo, lb, S, sv->L, sv->key_mask, sv->seg_prefix, sv->seg_len, nullptr, nullptr, 0, st, rg,
-                  (sv->Uc > 0 && i == d.n_layers - 1) ? &top : nullptr));
+                  (sv->Uc > 0 && i == d.n_layers - 1) ? &top : nullptr, sv->drop_on ? &drop_fwd : nullptr));
     if (fr) { res = xo; yin = nullptr; } else { res = lb.h; yin = Y; }
   }
   if (fr) {
@@ -1059,7 +1099,8 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
   { Carve cv(nullptr); cv.take<bf16_t>((size_t)R * dz_cols); cv.take<float>(VC > 0 ? (size_t)R * H : 1); cv.take<bf16_t>((size_t)R * H); cv.take<float>((size_t)R * H); cv.take<float>(MH); cv.take<bf16_t>(MH);
     cv.take<float>(MH); cv.take<bf16_t>(MH); cv.take<bf16_t>(MH); cv.take<bf16_t>((size_t)M * F); cv.take<bf16_t>((size_t)M * 2 * F); cv.take<bf16_t>(MH);
     cv.take<bf16_t>((size_t)M * 3 * H); cv.take<float>((size_t)S * nh * Lp); cv.take<bf16_t>((size_t)M * r); cv.take<bf16_t>((size_t)M * 2 * r);
-    cv.take<bf16_t>((size_t)M * 3 * r); cv.take<bf16_t>((size_t)M * r); cv.take<float>(sv->Uc > 0 ? MH : 1); cv.take<float>(tn_ws_floats); need = cv.off; }
+    cv.take<bf16_t>((size_t)M * 3 * r); cv.take<bf16_t>((size_t)M * r); cv.take<float>(sv->Uc > 0 ? MH : 1); cv.take<float>(tn_ws_floats);
+    cv.take<bf16_t>(sv->drop_on ? (size_t)M * (F + 6 * H) : 0); cv.take<bf16_t>(sv->drop_on ? (size_t)M * std::max(3 * H, F) : 0); need = cv.off; }
   const bool first = layer_hi == d.n_layers - 1;
   if (first) c->wgrad_det = 1;                        // of THIS backward: cleared below by any grouped wgrad launch that fell back to fp32 atomics
   if (R == 0) return 0;                               // no valid response token: every gradient of this pass is exactly zero (nothing flushed: trivially reproducible)
@@ -1076,6 +1117,13 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
   bf16_t* dt_ra = cv.take<bf16_t>((size_t)M * r);        // dT of the o projection (dt_r keeps the down projection's until the grouped wgrad)
   float* d_full = cv.take<float>(sv->Uc > 0 ? MH : 1);   // compact top layer: its residual gradient scattered back to every row
   float* tn_ws = cv.take<float>(tn_ws_floats);
+  // LoRA dropout: the masked copies of the layer's four Linear inputs, regenerated from the saved activations ([down | gate, up | o | q, k, v]: they stay
+  // untouched until the grouped wgrad launch), and the un-fused dT . A products of one Linear
+  const bool drop = sv->drop_on != 0;
+  bf16_t* xm_d = cv.take<bf16_t>(drop ? (size_t)M * (F + 6 * H) : 0);
+  bf16_t* xm_gu = xm_d + (size_t)M * F; bf16_t* xm_o = xm_gu + (size_t)M * 2 * H; bf16_t* xm_qkv = xm_o + MH;
+  bf16_t* du = cv.take<bf16_t>(drop ? (size_t)M * std::max(3 * H, F) : 0);
+  const LoraDropout& dp = sv->drop;
   const LoraOff o = lora_off(d);
   if (first) {
     if (!dlogp) return cbad(c, __func__, "null dlogp");
@@ -1127,11 +1175,25 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
       return hipSuccess;
     };
     // ---- MLP ----
+    // LoRA dropout (rate > 0 only; the else branches are the pass without it): dA reads the regenerated masked input, and the dT . A term of the input
+    // gradient - masked element by element - cannot be a K-tail of the dgrad product: it runs as its own product into du, lora_dropout_bwd_add adds it
+    const int32_t* drows = top ? sv->urow : nullptr;       // compact top layer: its rows hash with their row of the pass
+    if (drop) {
+      CK(launch_lora_dropout_fwd(b.act, xm_d, Mm, F, 1, dp, i, 6, drows, st));
+      CK(launch_lora_dropout_fwd(b.n2, xm_gu, Mm, H, 2, dp, i, 4, drows, st));
+      CK(launch_lora_dropout_fwd(top ? sv->attn_u : b.attn, xm_o, Mm, H, 1, dp, i, 3, drows, st));
+      CK(launch_lora_dropout_fwd(b.n1, xm_qkv, M, H, 3, dp, i, 0, nullptr, st));
+    }
     { GemmNTArgs g = gemm(dXb, H, wt + o.b_d, H, H, dt_r, r, 0, Mm, r); g.alpha = s; CK(run_gemm(c, g, st)); }
     CK(tn(dXb, H, b.t_d, r, gr + o.b_d, r, H, r, 0, 0, Mm));
-    CK(tn(dt_r, r, b.act, F, gr + o.a_d, F, r, F, 0, 0, Mm));
+    CK(tn(dt_r, r, drop ? xm_d : b.act, F, gr + o.a_d, F, r, F, 0, 0, Mm));
     const bool sb_staged = c->swiglu_bwd_staged;
-    if (F % 256 == 0 && (sb_staged || !c->swiglu_bwd_own_kernel)) {
+    if (drop) {
+      { GemmNTArgs g = gemm(dXb, H, w.wd_t, H, H, d_act, F, 0, Mm, F); CK(run_gemm(c, g, st)); }
+      { GemmNTArgs g = gemm(dt_r, r, wt + o.a_d, r, r, du, F, 0, Mm, F); CK(run_gemm(c, g, st)); }
+      CK(launch_lora_dropout_bwd_add(d_act, du, Mm, F, 1, dp, i, 6, drows, st));
+      CK(launch_silu_mul_bwd(d_act, b.gu, d_gu, Mm, F, st));
+    } else if (F % 256 == 0 && (sb_staged || !c->swiglu_bwd_own_kernel)) {
       // SwiGLU backward in the dgrad's epilogue: d_act never reaches HBM.  Default since round 5 in the DIRECT form (gate / up operands requested one
       // row block ahead of the accumulator read-out, lane-local math, gemm.hip w4_direct_epilogue_swiglu_bwd; context flag bit 14
       // keeps the two-kernel form).  Flag bit 6 = the LDS-staged form of rounds 3-4 (every operand load's latency exposed: 1016.9 vs 1013.3 ms per step
@@ -1145,16 +1207,30 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
     }
     { GemmNTArgs g = gemm(d_gu, 2 * F, wt + o.b_gu, F, F, dt_2r, 2 * r, 0, Mm, 2 * r); g.alpha = s; g.a1_group_n = r; g.a1_group_stride = F; CK(run_gemm(c, g, st)); }
     CK(tn(d_gu, 2 * F, b.t_gu, 2 * r, gr + o.b_gu, r, 2 * F, r, F, r, Mm));
+    if (drop) {
+      CK(tn(dt_2r, 2 * r, xm_gu, 2 * H, gr + o.a_gu, H, 2 * r, H, r, H, Mm));
+      { GemmNTArgs g = gemm(d_gu, 2 * F, w.wgu_t, 2 * F, 2 * F, d_n, H, 0, Mm, H); CK(run_gemm(c, g, st)); }
+      for (int j = 0; j < 2; ++j) { GemmNTArgs g = gemm(dt_2r + j * r, 2 * r, wt + o.a_gu + j * r, 2 * r, r, du + (size_t)j * H, 2 * H, 0, Mm, H); CK(run_gemm(c, g, st)); }
+      CK(launch_lora_dropout_bwd_add(d_n, du, Mm, H, 2, dp, i, 4, drows, st));
+    } else {
     CK(tn(dt_2r, 2 * r, b.n2, H, gr + o.a_gu, H, 2 * r, H, 0, 0, Mm));
     { GemmNTArgs g = gemm(d_gu, 2 * F, w.wgu_t, 2 * F, 2 * F, d_n, H, 0, Mm, H); tail(g, dt_2r, 2 * r, wt + o.a_gu, 2 * r, 2 * r); CK(run_gemm(c, g, st)); }
+    }
     CK(launch_rmsnorm_bwd(d_n, b.h, 1, w.ln2, b.rstd2, dX, 1, d_h, d_hb, Mm, H, st));
     // ---- attention ----
     { GemmNTArgs g = gemm(d_hb, H, wt + o.b_o, H, H, dt_ra, r, 0, Mm, r); g.alpha = s; CK(run_gemm(c, g, st)); }
     CK(tn(d_hb, H, b.t_o, r, gr + o.b_o, r, H, r, 0, 0, Mm));
-    CK(tn(dt_ra, r, top ? sv->attn_u : b.attn, H, gr + o.a_o, H, r, H, 0, 0, Mm));
+    CK(tn(dt_ra, r, drop ? xm_o : top ? sv->attn_u : b.attn, H, gr + o.a_o, H, r, H, 0, 0, Mm));
     {
       bf16_t* dst = top ? d_n : d_attn;            // d_n is free again: the norm backward above has consumed it
-      GemmNTArgs g = gemm(d_hb, H, w.wo_t, H, H, dst, H, 0, Mm, H); tail(g, dt_ra, r, wt + o.a_o, r, r); CK(run_gemm(c, g, st));
+      GemmNTArgs g = gemm(d_hb, H, w.wo_t, H, H, dst, H, 0, Mm, H);
+      if (drop) {
+        CK(run_gemm(c, g, st));
+        { GemmNTArgs gu_ = gemm(dt_ra, r, wt + o.a_o, r, r, du, H, 0, Mm, H); CK(run_gemm(c, gu_, st)); }
+        CK(launch_lora_dropout_bwd_add(dst, du, Mm, H, 1, dp, i, 3, drows, st));
+      } else {
+      tail(g, dt_ra, r, wt + o.a_o, r, r); CK(run_gemm(c, g, st));
+      }
       if (top) {                                   // gradient of the attention output: U rows carry one, every other row zero
         CK(hipMemsetAsync(d_attn, 0, MH * sizeof(bf16_t), st));
         CK(launch_scatter_rows(d_n, sv->urow, d_attn, H, Mm, H, st));
@@ -1176,12 +1252,19 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
                                        sv->ragged ? log2f(d.rope_theta) : 0.f));
     { GemmNTArgs g = gemm(dqkv, 3 * H, wt + o.b_qkv, H, H, dt_3r, 3 * r, 0, M, 3 * r); g.alpha = s; g.a1_group_n = r; g.a1_group_stride = H; CK(run_gemm(c, g, st)); }
     CK(tn(dqkv, 3 * H, b.t_qkv, 3 * r, gr + o.b_qkv, r, 3 * H, r, H, r, M));
-    CK(tn(dt_3r, 3 * r, b.n1, H, gr + o.a_qkv, H, 3 * r, H, 0, 0, M));
+    if (drop) CK(tn(dt_3r, 3 * r, xm_qkv, 3 * H, gr + o.a_qkv, H, 3 * r, H, r, H, M));
+    else CK(tn(dt_3r, 3 * r, b.n1, H, gr + o.a_qkv, H, 3 * r, H, 0, 0, M));
     { int ord = 1;      // what the launches of THIS list actually did (not a synthetic shape list): ordered reduce for every problem, or atomics somewhere
       CK(launch_gemm_tn_group(wg, nwg, ctx_flags(c), st, tn_ws_floats > 1 ? tn_ws : nullptr, tn_ws_floats > 1 ? tn_ws_floats * sizeof(float) : 0, &ord));
       if (!ord) c->wgrad_det = 0; }
     if (i > 0 || d_feats) {          // layer-0 input is the frozen embedding / image features: no further dgrad in the DPO stage
+      if (drop) {
+        { GemmNTArgs g = gemm(dqkv, 3 * H, w.wqkv_t, 3 * H, 3 * H, d_n, H, 0, M, H); CK(run_gemm(c, g, st)); }
+        for (int j = 0; j < 3; ++j) { GemmNTArgs g = gemm(dt_3r + j * r, 3 * r, wt + o.a_qkv + j * r, 3 * r, r, du + (size_t)j * H, 3 * H, 0, M, H); CK(run_gemm(c, g, st)); }
+        CK(launch_lora_dropout_bwd_add(d_n, du, M, H, 3, dp, i, 0, nullptr, st));
+      } else {
       { GemmNTArgs g = gemm(dqkv, 3 * H, w.wqkv_t, 3 * H, 3 * H, d_n, H, 0, M, H); tail(g, dt_3r, 3 * r, wt + o.a_qkv, 3 * r, 3 * r); CK(run_gemm(c, g, st)); }
+      }
       const float* dres = d_h;
       if (top) {                                   // residual gradient of the block: d_h holds it for the U rows only
         CK(hipMemsetAsync(d_full, 0, MH * sizeof(float), st));

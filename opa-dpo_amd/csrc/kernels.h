@@ -172,6 +172,23 @@ hipError_t launch_rope(bf16_t* qk, int ld, const float* cosb, const float* sinb,
                        float l2theta = 0.f);      // l2theta > 0 (with row_pos): table-free angles, the fused rotary epilogue's definition
 hipError_t launch_silu_mul_fwd(const bf16_t* gu, bf16_t* act, int rows, int F, hipStream_t st);
 hipError_t launch_silu_mul_bwd(const bf16_t* dact, const bf16_t* gu, bf16_t* dgu, int rows, int F, hipStream_t st);
+// ---- LoRA dropout (dropout.hip) ---------------------------------------------------------------------------------------------------------
+// keep(seed, call, layer, module, row, col) = philox4x32_10(counter, key)[col & 3] >= thr, thr = floor(p * 2^32), unsigned compare, with
+//   counter = (col >> 2, row, call & 0xffffffff, call >> 32)      key = (seed, layer * 8 + module)
+// seed < 2^32; module 0..6 = q, k, v, o, gate, up, down; row = index in the pass's own row list (ragged: compact row; padded: s * L + l; compact top
+// layer: urow[u], so the function does not depend on that optimisation); call = the host's per-training-forward counter (rank folded in).
+// One Philox call covers 4 consecutive columns of a row.  A kept element is bf16(x * scale), scale = fp32(1 / (1 - p)): ONE rounding, like the output
+// of a bf16 nn.Dropout; a dropped one is +0.  tests/dropout_ref.py restates all of this.
+struct LoraDropout { uint32_t thr, seed, call_lo, call_hi; float scale; };
+// 0, or 1 when p is outside [0, 1) or seed >= 2^32
+int lora_dropout_make(double p, uint64_t seed, uint64_t call, LoraDropout* out);
+// out [rows, g*K] = g masked, scaled copies of x [rows, K] side by side for modules module0 .. module0 + g - 1 (K % 8 == 0); row_idx (nullable, int32 [rows]) = the
+// row number each row hashes with
+hipError_t launch_lora_dropout_fwd(const bf16_t* x, bf16_t* out, int rows, int K, int g, const LoraDropout& dp, int layer, int module0, const int32_t* row_idx,
+                                   hipStream_t st);
+// dx [rows, K] += sum_j keep_j * u[:, j*K : (j+1)*K] * scale (fp32 sum in module order, one bf16 rounding)
+hipError_t launch_lora_dropout_bwd_add(bf16_t* dx, const bf16_t* u, int rows, int K, int g, const LoraDropout& dp, int layer, int module0, const int32_t* row_idx,
+                                       hipStream_t st);
 hipError_t launch_embed_splice(const int32_t* ids, const uint8_t* text_mask, const bf16_t* embed, const bf16_t* feats,
                                const int32_t* feat_row, const uint8_t* image_mask, void* x, int x_f32, uint8_t* key_mask,
                                int S, int n_txt, int P, int H, int image_token, hipStream_t st);

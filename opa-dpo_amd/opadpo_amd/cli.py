@@ -74,6 +74,8 @@ def build_args(ns: argparse.Namespace, world_size: Optional[int] = None) -> Simp
         if typ == "sbool":
             setattr(a, name.replace("-", "_"), _as_bool(getattr(a, name.replace("-", "_"))))
     a.AncPO = a.CoPO          # Quirk Q5 (opadpo_train_custom.py:202)
+    if not 0.0 <= float(getattr(a, "lora_drop", 0.0)) < 1.0:
+        raise ValueError(f"--lora_drop must be in [0, 1), got {a.lora_drop}")
     world = world_size if world_size is not None else int(os.environ.get("WORLD_SIZE", 1))
     a.world_size = world
     for total, per, out in (("rollout_batch_size", "rollout_per_device_batch_size", "rollout_accumulation_steps"),

@@ -52,6 +52,10 @@ def main(argv: Optional[List[str]] = None) -> None:
     for name, typ, _ in FLAGS:
         if typ == "sbool":
             setattr(ns, name, _as_bool(getattr(ns, name)))
+    if not 0.0 <= float(ns.lora_drop) < 1.0:
+        raise SystemExit(f"--lora_drop must be in [0, 1), got {ns.lora_drop}")
+    if ns.lora_drop > 0.0:
+        print("--lora_drop covers the LLM linears only: the CLIP tower's and the projector's LoRA train without dropout", flush=True)
     if ns.full_tune or not ns.lora_tune:
         raise SystemExit("only the LoRA recipe of run/train_opa.sh is built (lora_tune True, full_tune False)")
     if not (ns.tune_mm_mlp_adapter and ns.tune_base_model and ns.tune_vision_tower):
@@ -113,7 +117,8 @@ def main(argv: Optional[List[str]] = None) -> None:
     tr = SFTTrainer(engine, LoraAdapter(d, lora, dev, trainable=True), VisionLoraAdapter(d, lora, dev), response_len=t_len,
                     lr=ns.learning_rate, max_grad_norm=ns.max_grad_norm, weight_decay=ns.weight_decay, optimizer_mode=ns.optimizer_mode,
                     entropy_loss=ns.entropy_loss, entropy_mask_ratio=ns.entropy_mask_ratio, entropy_mask_method=ns.entropy_mask_method,
-                    entropy_loss_coef=ns.entropy_loss_coef, entropy_decay_coef=ns.entropy_decay_coef)
+                    entropy_loss_coef=ns.entropy_loss_coef, entropy_decay_coef=ns.entropy_decay_coef, lora_dropout=ns.lora_drop, seed=ns.seed,
+                    rank=rank, world=world)
     total = int(math.ceil(ns.num_train_epochs * steps_per_epoch)) if ns.max_steps <= 0 else ns.max_steps
     warm = int(math.ceil(ns.warmup_ratio * total))
     step, micro, log = 0, 0, []

@@ -227,8 +227,14 @@ class CtxEngine(LlavaEngine):
         self._call("opadpo_vision_encode", _ptr(px), B, _ptr(feats), L.stream())
         return feats
 
-    def seq_logprobs_fwd(self, adapter: Optional[LoraAdapter], batch: SeqBatch, feats: torch.Tensor, temperature: float, train: bool):
+    def seq_logprobs_fwd(self, adapter: Optional[LoraAdapter], batch: SeqBatch, feats: torch.Tensor, temperature: float, train: bool,
+                         lora_dropout: float = 0.0, dropout_call: int = 0, dropout_seed: int = 0):
+        """lora_dropout (training forwards only; a no-grad pass never drops): rate of the LoRA branch's input dropout, one mask per adapted Linear;
+        the masks are a pure function of (dropout_seed, dropout_call, layer, module, row, column) - the caller hands a `dropout_call` it never
+        reuses (AutoregressivePolicy / SFTTrainer count their training forwards) - and the backward of the returned handle regenerates them."""
         d = self.d
+        if not 0.0 <= lora_dropout < 1.0:
+            raise ValueError(f"lora_dropout must be in [0, 1), got {lora_dropout}")
         S, n_txt = batch.ids.shape
         T, K = batch.T, batch.K
         self._ensure_rope(n_txt + d.n_patches - 1)
@@ -239,6 +245,8 @@ class CtxEngine(LlavaEngine):
         handle = C.c_void_p()
         feats = feats.contiguous()
         plan = getattr(batch, "row_plan", None) if self.ragged else None       # CPU int32 [S, K+1] (policy.build_batch) or None = padded rows
+        if train and lora_dropout > 0.0:               # rate 0: nothing is set, the pass is the one without the feature
+            self._call("opadpo_ctx_set_lora_dropout", float(lora_dropout), int(dropout_seed) & 0xffffffff, int(dropout_call))
         self._call("opadpo_seq_logprobs_fwd", slot, _ptr(batch.ids), _ptr(batch.text_mask), _ptr(batch.feat_row), _ptr(batch.image_mask),
                    _ptr(feats), S, n_txt, T, K, float(temperature), int(train), _ptr(logp), _ptr(ent), C.byref(handle),
                    plan.data_ptr() if plan is not None else None, L.stream())

@@ -47,6 +47,8 @@ SIGNATURES = {
     "opadpo_rope": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _p],
     "opadpo_silu_mul_fwd": [_p, _p, _i, _i, _p],
     "opadpo_silu_mul_bwd": [_p, _p, _p, _i, _i, _p],
+    "opadpo_lora_dropout_fwd": [_p, _p, _i, _i, _i, _d, _u64, _u64, _i, _i, _p, _p],
+    "opadpo_lora_dropout_bwd_add": [_p, _p, _i, _i, _i, _d, _u64, _u64, _i, _i, _p, _p],
     "opadpo_embed_splice": [_p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
     "opadpo_im2col": [_p, _p, _i, _i, _i, _i, _p],
     "opadpo_vision_embed": [_p, _p, _p, _p, _i, _i, _i, _p],
@@ -86,6 +88,7 @@ SIGNATURES.update({
     "opadpo_vision_encode": [_p, _p, _i, _p, _p],
     "opadpo_seq_logprobs_fwd": [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p],
     "opadpo_seq_logprobs_bwd": [_p, _p, _p, _p, _p, _i, _i, _p],
+    "opadpo_ctx_set_lora_dropout": [_p, _d, _u64, _u64],
     "opadpo_saved_release": [_p, _p],
     "opadpo_saved_residual": [_p, _p, _i, _p, _p, _p],
     "opadpo_decode_begin": [_p, _i, _p, _p, _p, _i, _i, _i, _f, _i, _f, _u64, _i, _i, _i, _p, _p],

@@ -479,10 +479,12 @@ class LlavaEngine:
             L.gemm_nt(act, w["wd"], xo if ydef is None else ydef, residual=h if ydef is None else None)
 
     def seq_logprobs_fwd(self, adapter: LoraAdapter, batch: SeqBatch, feats: torch.Tensor, temperature: float,
-                         train: bool):
+                         train: bool, lora_dropout: float = 0.0, dropout_call: int = 0, dropout_seed: int = 0):
         """S stacked sequences -> (logp [S,T] fp32, entropy [S,T] fp32, Saved).  Mirrors
         rl_models.py:114-132: one batched LM forward, logits[:, -T-1:-1] / temperature, labels =
         ids[:, -T:], log-softmax gather + entropy, both masked by response != pad."""
+        if train and lora_dropout > 0.0:
+            raise L.OpadpoError("LoRA dropout runs on the context path only (ctx.CtxEngine); the op-level engine has no dropout schedule")
         d, b = self.d, self.base
         st = L.stream()
         S, n_txt = batch.ids.shape

@@ -48,7 +48,7 @@ def host_row_plan(queries: torch.Tensor, queries_attn_masks: torch.Tensor, respo
 class _SeqLogprobs(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, policy, batch, feats, temperature):
-        logp, ent, saved = policy.engine.seq_logprobs_fwd(policy.adapter, batch, feats, temperature, train=True)
+        logp, ent, saved = policy.engine.seq_logprobs_fwd(policy.adapter, batch, feats, temperature, train=True, **policy.next_dropout())
         ctx.policy, ctx.saved = policy, saved
         policy._pending_bwd += 1
         ctx.mark_non_differentiable(ent)
@@ -83,7 +83,25 @@ class AutoregressivePolicy(torch.nn.Module):
         # autograd anchor: a leaf that requires grad so that the HIP forward gets a grad_fn
         self._anchor = torch.zeros(1, device=engine.dev, requires_grad=True) if adapter.trainable else None
         self._pending_bwd = 0             # training forwards whose backward has not run yet
+        # LoRA dropout (PEFT lora_dropout; --lora_drop): applied by the TRAINING forward only (grad mode on, trainable adapter) - rollouts, the frozen
+        # reference policy and generation never drop.  Every training forward takes the next value of `dropout_calls` (rank folded in), so no two
+        # micro-batches or ranks share masks; the trainer saves / restores the counter with its checkpoints.
+        self.lora_dropout, self.dropout_seed, self.dropout_calls = 0.0, 0, 0
+        self.dropout_rank, self.dropout_world = 0, 1
         self.layer_done_hook = None       # callable(layer) set by the trainer on the gradient-sync micro-batch (optim.launch_bucket)
+
+    def set_lora_dropout(self, rate: float, seed: int = 0, rank: int = 0, world: int = 1) -> None:
+        if not 0.0 <= rate < 1.0:
+            raise ValueError(f"lora_dropout must be in [0, 1), got {rate}")
+        self.lora_dropout, self.dropout_seed, self.dropout_rank, self.dropout_world = float(rate), int(seed), int(rank), int(world)
+
+    def next_dropout(self) -> dict:
+        """Keyword arguments of engine.seq_logprobs_fwd for the next training forward (empty at rate 0: the call is the one without dropout)."""
+        if self.lora_dropout <= 0.0:
+            return {}
+        call = self.dropout_calls * self.dropout_world + self.dropout_rank
+        self.dropout_calls += 1
+        return dict(lora_dropout=self.lora_dropout, dropout_call=call, dropout_seed=self.dropout_seed)
 
     def build_batch(self, queries, queries_attn_masks, responses: Dict[str, torch.Tensor], row_lead=None, row_lens=None):
         """-> (response keys, SeqBatch).  The reference policy and the trained policy of a step see the SAME collated tensors

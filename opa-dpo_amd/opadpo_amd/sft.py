@@ -41,14 +41,18 @@ class SFTTrainer:
     def __init__(self, engine: LlavaEngine, llm_adapter: LoraAdapter, vis_adapter: VisionLoraAdapter, *, response_len: int,
                  lr: float = 2e-5, max_grad_norm: Optional[float] = 1.0, weight_decay: float = 0.0, optimizer_mode: str = "allreduce",
                  entropy_loss: bool = False, entropy_mask_ratio: float = 0.2, entropy_mask_method: str = "random",
-                 entropy_loss_coef: float = 1.0, entropy_decay_coef: float = 1.0):
+                 entropy_loss_coef: float = 1.0, entropy_decay_coef: float = 1.0, lora_dropout: float = 0.0, seed: int = 0, rank: int = 0,
+                 world: int = 1):
         assert llm_adapter.trainable
         self.entropy_loss, self.entropy_mask_ratio, self.entropy_mask_method = entropy_loss, entropy_mask_ratio, entropy_mask_method
         self.entropy_loss_coef, self.entropy_decay_coef = entropy_loss_coef, entropy_decay_coef
         self.last = {}
         self.engine, self.llm, self.vis = engine, llm_adapter, vis_adapter
         self.vision = VisionTrainPath(engine.base, vis_adapter)
-        self._policy = AutoregressivePolicy(engine, llm_adapter, response_len)      # batch building only
+        self._policy = AutoregressivePolicy(engine, llm_adapter, response_len)      # batch building + the LoRA dropout call counter
+        # --lora_drop: dropout on the LLM linears' LoRA branches of both training forwards (the CLIP tower's and the projector's LoRA train without it)
+        self.lora_dropout = float(lora_dropout)
+        self._policy.set_lora_dropout(self.lora_dropout, seed, rank, world)
         kw = dict(lr=lr, max_grad_norm=max_grad_norm, weight_decay=weight_decay, mode=optimizer_mode)
         self.opt_llm = FlatAdamW(llm_adapter.master, llm_adapter.grad, llm_adapter.work, **kw)
         self.opt_vis = FlatAdamW(vis_adapter.master, vis_adapter.grad, vis_adapter.work, **kw)
@@ -64,7 +68,7 @@ class SFTTrainer:
         mask = (responses.to(dev) != PAD_ID)
         n = mask.sum().clamp_min(1).float()
         feats, vsv = self.vision.forward(images)
-        logp, ent, sv = eng.seq_logprobs_fwd(self.llm, batch, feats.view(B, d.n_patches, d.hidden), 1.0, train=True)
+        logp, ent, sv = eng.seq_logprobs_fwd(self.llm, batch, feats.view(B, d.n_patches, d.hidden), 1.0, train=True, **self._policy.next_dropout())
         loss = -(logp * mask).sum() / n
         self.last = {"base_sft_loss": float(loss), "mask_sft_loss": 0.0, "entropy_loss": 0.0}
         d_ent = None
@@ -87,7 +91,8 @@ class SFTTrainer:
                 batch2 = batch
                 feats2, vsv2 = self.vision.forward(masked_images)
                 d_feats2 = torch.zeros(B, d.n_patches, d.hidden, dtype=torch.float32, device=dev)
-            logp2, ent2, sv2 = eng.seq_logprobs_fwd(self.llm, batch2, feats2.view(B, d.n_patches, d.hidden), 1.0, train=True)
+            logp2, ent2, sv2 = eng.seq_logprobs_fwd(self.llm, batch2, feats2.view(B, d.n_patches, d.hidden), 1.0, train=True,
+                                                    **self._policy.next_dropout())
             per_row = mask.sum(1).clamp_min(1).float()
             e_loss = (-((ent2 - ent) * mask).sum(1) / per_row).mean()
             self.entropy_loss_coef *= self.entropy_decay_coef                      # opa_trainer.py:119 (decay applied before use)
@@ -127,7 +132,7 @@ class SFTTrainer:
         state.update(self.vis.to_peft_state())
         torch.save(state, os.path.join(directory, "adapter_model.bin"))
         d = self.engine.d
-        cfg = {"peft_type": "LORA", "task_type": "CAUSAL_LM", "r": d.lora_r, "lora_alpha": d.lora_alpha, "lora_dropout": 0.0, "bias": "none",
+        cfg = {"peft_type": "LORA", "task_type": "CAUSAL_LM", "r": d.lora_r, "lora_alpha": d.lora_alpha, "lora_dropout": self.lora_dropout, "bias": "none",
                "target_modules": ["q_proj", "k_proj", "v_proj", "o_proj", "out_proj", "gate_proj", "up_proj", "down_proj", "fc1", "fc2",
                                   "mm_projector.0", "mm_projector.2"],
                "base_model_name_or_path": base_model_name_or_path, "inference_mode": True, "fan_in_fan_out": False}

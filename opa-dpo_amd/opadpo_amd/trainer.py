@@ -56,7 +56,7 @@ def get_last_checkpoint(checkpoint_dir: str):
 
 
 def save_adapter(adapter, directory: str, dims, base_model_name_or_path: str = "", extra_state: Optional[Dict[str, torch.Tensor]] = None,
-                 source_config: Optional[dict] = None) -> None:
+                 source_config: Optional[dict] = None, lora_dropout: float = 0.0) -> None:
     """PEFT-0.5 layout (dpo_trainer.py:1047-1095): adapter_model.bin (torch pickle, keys without the adapter name) +
     adapter_config.json with inference_mode forced True.
 
@@ -80,7 +80,7 @@ def save_adapter(adapter, directory: str, dims, base_model_name_or_path: str = "
             if mod not in targets:
                 targets.append(mod)
     cfg = {"peft_type": "LORA", "task_type": "CAUSAL_LM", "r": dims.lora_r, "lora_alpha": dims.lora_alpha,
-           "lora_dropout": 0.0, "bias": "none", "target_modules": targets,
+           "lora_dropout": float(lora_dropout), "bias": "none", "target_modules": targets,
            "base_model_name_or_path": base_model_name_or_path, "inference_mode": True, "fan_in_fan_out": False,
            "init_lora_weights": True, "modules_to_save": None, "layers_to_transform": None,
            "layers_pattern": None, "revision": None}
@@ -114,6 +114,9 @@ class DPOTrainer:
                                    bucket_bounds=layer_buckets(ad.layer_numel, self.engine.d.n_layers, layers_per_bucket),
                                    exchange_dtype=exchange_dtype, **(optimizer_kwargs or {}))
         self.optimizer.release_full_master(ad)       # ZeRO-1 across ranks: the fp32 master lives in this rank's slices only
+        # --lora_drop: dropout on the policy's TRAINING forward only (compute_policy_loss); rollout() runs under no_grad and the reference policy is frozen
+        self.lora_dropout = float(getattr(args, "lora_drop", 0.0) or 0.0)
+        policy.set_lora_dropout(self.lora_dropout, getattr(args, "seed", 42), self.rank, self.world)
         self.sched_step = 0
         self.total_sched_steps = 1
         self.log_history: List[dict] = []
@@ -311,8 +314,10 @@ class DPOTrainer:
         if self.is_main:
             os.makedirs(output_dir, exist_ok=True)
             save_adapter(self.policy.adapter, os.path.join(output_dir, ADAPTER_MODEL_DIR, "lora_policy"), self.engine.d,
-                         getattr(self.args, "base_model_name", ""), self.frozen_adapter_state, self.source_adapter_config)
-            torch.save({"optimizer": opt_sd, "sched_step": self.sched_step}, os.path.join(output_dir, OPTIMIZER_NAME))
+                         getattr(self.args, "base_model_name", ""), self.frozen_adapter_state, self.source_adapter_config, self.lora_dropout)
+            # dropout_calls: the policy's training-forward counter (the same on every rank) - a resumed run goes on with fresh dropout masks
+            torch.save({"optimizer": opt_sd, "sched_step": self.sched_step, "dropout_calls": self.policy.dropout_calls},
+                       os.path.join(output_dir, OPTIMIZER_NAME))
             torch.save({"last_epoch": self.sched_step, "total": self.total_sched_steps},
                        os.path.join(output_dir, SCHEDULER_NAME))
             parent = os.path.dirname(output_dir.rstrip("/"))
@@ -331,6 +336,7 @@ class DPOTrainer:
             sd = torch.load(opt, map_location="cpu")
             self.optimizer.load_state_dict(sd["optimizer"])
             self.sched_step = int(sd["sched_step"])
+            self.policy.dropout_calls = int(sd.get("dropout_calls", 0))
             self._set_lr()
             if self.policy.adapter.trainable:
                 self.policy.adapter.refresh_transposed()
