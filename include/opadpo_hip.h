@@ -276,6 +276,19 @@ int opadpo_attn_decode_fused(const uint16_t* qkv, int ld, const float* cos_tab, 
 int opadpo_sample(const float* logits, int ldl, int rows, int V, float temperature, int top_k, float top_p,
                   uint64_t seed, uint64_t step, const int32_t* step_ptr, uint8_t* finished, int pad_id, int eos_id,
                   int32_t* out, int32_t* history, void* stream);
+/* Logits processors of the yes/no evaluation generator (eval_llava_rlhf_coco/model_vqa_logit.py), for rows <= 64 and at most
+ * OPADPO_MAX_LOGIT_IDS table entries.  ids (int32) / bias (fp32) are DEVICE arrays; ids_host is the host copy of ids, checked before anything is
+ * launched: every id in [0, V), and no id twice in a bias table.
+ * opadpo_logit_bias_add: logits[row, ids[e]] += bias[e] for every row - HF's sequence_bias with one-token sequences; call it before
+ * opadpo_sample (logits processors run before temperature / top-k / top-p).  n = 0 launches nothing.
+ * opadpo_gather_scores: scores [rows, m] fp32 = the processed scores HF's generate(output_scores=True) records for a sampled step:
+ * logit / temperature, then the top-k and top-p cuts of opadpo_sample's order; a token that is cut reads -inf.  temperature = 0 (greedy
+ * decoding in this library): the logit itself, nothing cut.  ids may repeat.  m = 0 launches nothing. */
+#define OPADPO_MAX_LOGIT_IDS 64
+int opadpo_logit_bias_add(float* logits, int ldl, int rows, int V, const int32_t* ids, const float* bias, const int32_t* ids_host, int n,
+                          void* stream);
+int opadpo_gather_scores(const float* logits, int ldl, int rows, int V, const int32_t* ids, const int32_t* ids_host, int m, float temperature,
+                         int top_k, float top_p, float* scores, void* stream);
 
 /* Beam search (HF GenerationMixin._beam_search with do_sample=False, num_return_sequences=1, length_penalty=1.0, early_stopping=False).
  * B items of k beams each; rows = B*k <= 64, 1 <= k <= OPADPO_MAX_BEAMS.  Row i is beam i % k of item i / k.
@@ -447,6 +460,17 @@ int opadpo_saved_residual(opadpo_ctx* ctx, const opadpo_saved* saved, int layer,
 int opadpo_decode_begin(opadpo_ctx* ctx, int adapter_id, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats, int B, int Q,
                         int max_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, int eos_id, int pad_id, int suppress_eos,
                         int32_t* history, void* stream);
+/* Logit bias and first-token scores of the NEXT opadpo_decode_begin of this context (model_vqa_logit.py: sequence_bias / output_scores).
+ * bias_ids / bias [n] and score_ids [m] are HOST arrays (copied; n, m <= OPADPO_MAX_LOGIT_IDS, ids in [0, vocab), bias ids distinct).
+ * n > 0: every step of that generation - the prefill head that produces token 0 included - adds bias[e] to the logit of bias_ids[e] in every
+ * row before temperature / top-k / top-p (one more launch per step, part of the captured step under use_graph).  m > 0: after token 0 the
+ * processed step-0 scores of score_ids go to scores [B, m] fp32 (caller-owned device memory, like history) as opadpo_gather_scores defines them
+ * with the generation's temperature / top_k / top_p; scores_raw != 0: the biased logits themselves (greedy decoding, which the host asks for
+ * as top_k = 1).  opadpo_decode_begin reads the setting and opadpo_decode_end clears it: the generation after that runs without either unless
+ * this is called again.  n = m = 0 clears it; a generation without it issues exactly the launches it issued before this entry point existed.
+ * opadpo_decode_beam_begin refuses an armed context. */
+int opadpo_ctx_set_logit_processors(opadpo_ctx* ctx, const int32_t* bias_ids, const float* bias, int n, const int32_t* score_ids, int m,
+                                    float* scores, int scores_raw);
 /* one more token for every row: all launches of a step, asynchronous */
 int opadpo_decode_step(opadpo_ctx* ctx, void* stream);
 /* n_steps more tokens.  use_graph = 0: the launches of every step are issued from the library's own loop (no host work between

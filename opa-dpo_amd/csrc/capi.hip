@@ -461,6 +461,21 @@ int opadpo_sample(const float* logits, int ldl, int rows, int V, float temperatu
                             history, S(stream)),
               "opadpo_sample");
 }
+// the launch wrappers refuse (hipErrorInvalidValue, nothing launched) what the message lists; the text is written here, where the caller reads it
+int opadpo_logit_bias_add(float* logits, int ldl, int rows, int V, const int32_t* ids, const float* bias, const int32_t* ids_host, int n,
+                          void* stream) {
+  const hipError_t e = launch_logit_bias_add(logits, ldl, rows, V, ids, bias, ids_host, n, S(stream));
+  if (e == hipErrorInvalidValue)
+    return bad("opadpo_logit_bias_add", "need rows <= 64, 0 <= n <= 64, ldl >= V, non-null logits / ids / bias / ids_host, distinct ids inside [0, V)");
+  return done(e, "opadpo_logit_bias_add");
+}
+int opadpo_gather_scores(const float* logits, int ldl, int rows, int V, const int32_t* ids, const int32_t* ids_host, int m, float temperature,
+                         int top_k, float top_p, float* scores, void* stream) {
+  const hipError_t e = launch_gather_scores(logits, ldl, rows, V, ids, ids_host, m, temperature, top_k, top_p, scores, S(stream));
+  if (e == hipErrorInvalidValue)
+    return bad("opadpo_gather_scores", "need rows <= 64, 0 <= m <= 64, ldl >= V, temperature >= 0, non-null logits / ids / ids_host / scores, ids inside [0, V)");
+  return done(e, "opadpo_gather_scores");
+}
 
 // ---- gradient exchange for binders that do not go through torch.distributed (opadpo_allreduce_grads) -----------------------
 // The collective library is NOT linked: the entry points resolve ncclAllReduce / ncclReduceScatter / ncclAllGather at first use from whatever RCCL the

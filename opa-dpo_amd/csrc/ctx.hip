@@ -250,6 +250,8 @@ struct opadpo_ctx {
                                                   // CoPO's K = 2 masked pass does not inherit the K = 3 pass's worst case
   std::vector<opadpo_saved*> live;
   bool next_drop_on = false; LoraDropout next_drop{};      // opadpo_ctx_set_lora_dropout: consumed by the next training forward
+  // opadpo_ctx_set_logit_processors: host copies, read by the next opadpo_decode_begin and cleared by opadpo_decode_end
+  struct LogitArm { std::vector<int32_t> bias_ids, score_ids; std::vector<float> bias; float* scores = nullptr; int raw = 0; } next_logit;
   // dispatch: opadpo_ctx_set_flags(gemm_variant, use_tr), parsed once; the use_tr bits below are off for a negative word
   KernelOverrides kernel;                         // gemm_variant, bits 0, 3 and 8 over the process flags (resolve_flags, per launch)
   bool streaming_dec_gemm = false;                // bit 5: decode steps of 9..64 sequences keep the 8/16-row streaming GEMMs
@@ -273,6 +275,9 @@ struct opadpo_ctx {
     float *hb, *rstd, *logits; int32_t *cur_tok, *step_d, *pos_d; uint8_t* finished; void* ws; size_t ws_bytes;
     float *part_o, *part_d; int split_o = 1, split_d = 1; bool use64 = false;      // K-split partial tiles of the 9..64-token decode GEMMs
     int32_t* history; float temperature; int top_k; float top_p; uint64_t seed; int eos_id, pad_id, suppress_eos;
+    // logit bias of every step and the step-0 scores (opadpo_ctx_set_logit_processors): `logit` = the host copy this generation took, the device tables
+    // live in the arena (carved only when armed)
+    opadpo_ctx::LogitArm logit; int32_t *bias_ids = nullptr, *score_ids = nullptr; float* bias = nullptr;
     // beam decode (opadpo_decode_beam_begin): B = items * beams rows; kc / vc = the items' prefix caches [items, nh, Lp, hd], ks / vs = the
     // rows' suffix caches [B, nh, max_new, hd]; finished = per-item done flags; bs = selection state (decode.hip beam_update_kernel)
     int beams = 0, items = 0; bf16_t *ks = nullptr, *vs = nullptr; BeamState bs{};
@@ -715,6 +720,25 @@ int opadpo_ctx_set_lora_dropout(opadpo_ctx* c, double p, uint64_t seed, uint64_t
   LoraDropout dp;
   if (lora_dropout_make(p, seed, call, &dp)) return cbad(c, __func__, "need 0 <= p < 1 and seed < 2^32");
   c->next_drop = dp; c->next_drop_on = true;
+  return 0;
+}
+
+int opadpo_ctx_set_logit_processors(opadpo_ctx* c, const int32_t* bias_ids, const float* bias, int n, const int32_t* score_ids, int m, float* scores,
+                                    int scores_raw) {
+  if (!c) return (int)hipErrorInvalidValue;
+  if (n < 0 || n > OPADPO_MAX_LOGIT_IDS || m < 0 || m > OPADPO_MAX_LOGIT_IDS) return cbad(c, __func__, "at most OPADPO_MAX_LOGIT_IDS (64) bias entries and score ids");
+  if ((n > 0 && (!bias_ids || !bias)) || (m > 0 && (!score_ids || !scores))) return cbad(c, __func__, "null table with entries to read");
+  for (int i = 0; i < n; ++i) {
+    if (bias_ids[i] < 0 || bias_ids[i] >= c->d.vocab) return cbad(c, __func__, "bias token id outside [0, vocab)");
+    for (int j = 0; j < i; ++j)
+      if (bias_ids[j] == bias_ids[i]) return cbad(c, __func__, "duplicate bias token id");
+  }
+  for (int i = 0; i < m; ++i)
+    if (score_ids[i] < 0 || score_ids[i] >= c->d.vocab) return cbad(c, __func__, "score token id outside [0, vocab)");
+  opadpo_ctx::LogitArm a;
+  a.bias_ids.assign(bias_ids, bias_ids + n); a.bias.assign(bias, bias + n); a.score_ids.assign(score_ids, score_ids + m);
+  a.scores = m > 0 ? scores : nullptr; a.raw = scores_raw;
+  c->next_logit = std::move(a);
   return 0;
 }
 
@@ -1303,6 +1327,9 @@ static hipError_t decode_head(opadpo_ctx* c, const float* src_f32, const float* 
     hipLaunchKernelGGL(add_i32_kernel, dim3(1), dim3(64), 0, st, D.step_d, 1);
     return hipGetLastError();
   }
+  if (!D.logit.bias_ids.empty() &&      // HF order: logits processors (the bias) before the warpers (temperature / top-k / top-p in the sampler)
+      (e = launch_logit_bias_add(D.logits, d.vocab, D.B, d.vocab, D.bias_ids, D.bias, D.logit.bias_ids.data(), (int)D.logit.bias_ids.size(), st)) != hipSuccess)
+    return e;
   if (D.suppress_eos) {
     hipLaunchKernelGGL(set_column_f32_kernel, g1(D.B), dim3(256), 0, st, D.logits, d.vocab, D.B, D.eos_id, -INFINITY);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -1444,6 +1471,8 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
     D.ws = cv.take<uint8_t>(std::max<size_t>(D.ws_bytes, 4));
     D.part_o = cv.take<float>(D.use64 ? (size_t)D.split_o * B * H : 1);
     D.part_d = cv.take<float>(D.use64 ? (size_t)D.split_d * B * H : 1);
+    if (!D.logit.bias_ids.empty()) { D.bias_ids = cv.take<int32_t>(D.logit.bias_ids.size()); D.bias = cv.take<float>(D.logit.bias.size()); }
+    if (!D.logit.score_ids.empty()) D.score_ids = cv.take<int32_t>(D.logit.score_ids.size());
     return cv.off;
   };
   D.bytes = layout(nullptr);
@@ -1510,6 +1539,12 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
     CKD(hipMemsetAsync(s.table, 0, 2 * (size_t)s.table_stride * sizeof(int32_t), st));
     CKD(hipMemsetAsync(s.bp, 0, 2 * (size_t)max_new_tokens * B * sizeof(int32_t), st));
   }
+  if (!D.logit.bias_ids.empty()) {         // D.logit outlives the copies (it is cleared by opadpo_decode_end); the synchronisation below covers them
+    CKD(hipMemcpyAsync(D.bias_ids, D.logit.bias_ids.data(), D.logit.bias_ids.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    CKD(hipMemcpyAsync(D.bias, D.logit.bias.data(), D.logit.bias.size() * sizeof(float), hipMemcpyHostToDevice, st));
+  }
+  if (!D.logit.score_ids.empty())
+    CKD(hipMemcpyAsync(D.score_ids, D.logit.score_ids.data(), D.logit.score_ids.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
   { const int32_t p0 = Lp - 1; CKD(hipMemcpyAsync(D.pos_d, &p0, sizeof(int32_t), hipMemcpyHostToDevice, st)); CKD(hipStreamSynchronize(st)); }
   // history [max_new, B] starts as pad
   if (history) {
@@ -1519,6 +1554,9 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
   }
   // token 0 from the prefill logits (beam decode: step 0 of the search on the items' rows)
   CKD(fr ? decode_head(c, D.hs, nullptr, 0, st, items) : decode_head(c, D.hs, D.x, 1, st, items));
+  if (!D.logit.score_ids.empty())          // step-0 scores: D.logits still holds what the sampler just read (bias added, EOS column suppressed)
+    CKD(launch_gather_scores(D.logits, V, B, V, D.score_ids, D.logit.score_ids.data(), (int)D.logit.score_ids.size(), D.logit.raw ? 0.f : temperature,
+                             top_k, top_p, D.logit.scores, st));
 #undef CKD
   ctx_free(c, parena, pbytes);
   return 0;
@@ -1528,11 +1566,15 @@ int opadpo_decode_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const
                         int max_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, int eos_id, int pad_id, int suppress_eos,
                         int32_t* history, void* stream) {
   if (!c) return (int)hipErrorInvalidValue;
+  // the setting is for THIS call, accepted or refused; opadpo_decode_end (below, and at the end of the generation) clears what is left of it
+  opadpo_ctx::LogitArm arm = std::move(c->next_logit);
+  c->next_logit = {};
   if (!weights_ready(c)) return cbad(c, __func__, "LLM weights not set");
   if (adapter_id < 0 || adapter_id >= OPADPO_MAX_ADAPTERS) return cbad(c, __func__, "adapter id out of range");
   if (!ids || !text_mask || !feats || !history || B <= 0 || Q <= 0 || max_new_tokens <= 0 || temperature <= 0.f) return cbad(c, __func__, "null operand or bad shape");
   if (B > 64) return cbad(c, __func__, "decode batch above 64 per device is not supported by the weight-streaming GEMMs");
   opadpo_decode_end(c);
+  c->dec.logit = std::move(arm);
   return decode_begin_impl(c, __func__, adapter_id, ids, text_mask, feats, B, Q, 0, max_new_tokens, temperature, top_k, top_p, seed, eos_id, pad_id,
                            suppress_eos, history, (hipStream_t)stream);
 }
@@ -1546,6 +1588,10 @@ int opadpo_decode_beam_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, 
   if (adapter_id < 0 || adapter_id >= OPADPO_MAX_ADAPTERS) return cbad(c, __func__, "adapter id out of range");
   if (!ids || !text_mask || !feats || Q <= 0 || max_new_tokens <= 0) return cbad(c, __func__, "null operand or bad shape");
   if (c->d.vocab < 2 * k || c->d.vocab > 32768) return cbad(c, __func__, "beam search needs 2 * num_beams <= vocab <= 32768");
+  if (!c->next_logit.bias_ids.empty() || !c->next_logit.score_ids.empty()) {
+    c->next_logit = {};                            // consumed by the refusal: the generation after it runs without
+    return cbad(c, __func__, "logit bias / first-token scores (opadpo_ctx_set_logit_processors) are not supported under beam search");
+  }
   opadpo_decode_end(c);
   return decode_begin_impl(c, __func__, adapter_id, ids, text_mask, feats, B, Q, k, max_new_tokens, 1.0f, 0, 1.0f, 0, eos_id, pad_id, 0, nullptr,
                            (hipStream_t)stream);
@@ -1676,6 +1722,8 @@ int opadpo_decode_end(opadpo_ctx* c) {
   if (D.cap_stream) { (void)hipStreamSynchronize(D.cap_stream); }
   if (D.active) { ctx_free(c, D.arena, D.bytes); D.arena = nullptr; D.active = false; }
   D.beams = 0; D.items = 0;
+  D.logit = {}; D.bias_ids = nullptr; D.score_ids = nullptr; D.bias = nullptr;
+  c->next_logit = {};
   return 0;
 }
 

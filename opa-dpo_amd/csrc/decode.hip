@@ -657,6 +657,91 @@ __global__ __launch_bounds__(SAMP_T) void sample_kernel_fast(const float* logits
   }
 }
 
+// ---- logits processors of the yes/no evaluation generator (eval_llava_rlhf_coco/model_vqa_logit.py:107-121,182-202) -----------------------
+// logit_bias_add: HF's sequence_bias restricted to one-token sequences = an additive bias on those tokens' logits, applied to the fp32 logits
+// [rows, V] of a step BEFORE temperature / top-k / top-p (logits processors run before the warpers) and to every row, finished ones included
+// (they emit pad whatever their logits are).  One thread per (row, table entry); the host refuses duplicate ids, so no two threads share an
+// address.  ids outside [0, V) never reach the kernel (launch_logit_bias_add); the guard keeps a stale table from writing out of the row.
+__global__ __launch_bounds__(256) void logit_bias_add_kernel(float* logits, int ldl, int rows, int V, const int32_t* ids, const float* bias, int n) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= rows * n) return;
+  const int row = idx / n, e = idx - row * n;
+  const int id = ids[e];
+  if ((unsigned)id >= (unsigned)V) return;
+  logits[(size_t)row * ldl + id] += bias[e];
+}
+
+// gather_scores: scores[row, j] = the PROCESSED score of token ids[j] as HF's generate(output_scores=True) records it for a sampled step:
+// v = logit / temperature (the bias is in the logits already), then top-k (keep v >= the k-th largest v, ties kept), then top-p on the
+// softmax of what top-k kept (ascending cumulative mass <= 1 - top_p is cut, the largest token always stays); a cut token reads -inf.
+// temperature == 0 (this tree's greedy): the raw logit, nothing cut.  One workgroup per row; runs once per generation, so the top-k
+// threshold is the plain 32-step bitwise descent of sample_kernel_generic and every requested id costs one sweep of the row.  The softmax
+// masses are summed in fp64 (a token at the top-p boundary is decided by mass, not by the order of an fp32 sum).  Duplicate ids are fine.
+__global__ __launch_bounds__(256) void gather_scores_kernel(const float* logits, int ldl, int V, const int32_t* ids, int m, float temperature,
+                                                            int top_k, float top_p, float* scores) {
+  __shared__ float red[4];
+  __shared__ double redd[4];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* z = logits + (size_t)row * ldl;
+  float* out = scores + (size_t)row * m;
+  if (temperature == 0.f) {
+    if (tid < m) {
+      const int id = ids[tid];
+      out[tid] = (unsigned)id < (unsigned)V ? z[id] : NAN;
+    }
+    return;
+  }
+  auto block_sum_f64 = [&](double x) -> double {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    __syncthreads();
+    if ((tid & 63) == 0) redd[tid >> 6] = x;
+    __syncthreads();
+    return redd[0] + redd[1] + redd[2] + redd[3];
+  };
+  float mx = -INFINITY;
+  for (int i = tid; i < V; i += 256) mx = fmaxf(mx, z[i] / temperature);
+  mx = block_max_256(mx, red);
+  uint32_t thr = 0;   // top-k keeps tokens with key >= thr
+  if (top_k > 0 && top_k < V) {
+    for (int bit = 31; bit >= 0; --bit) {
+      const uint32_t cand = thr | (1u << bit);
+      float cnt = 0.f;
+      for (int i = tid; i < V; i += 256) cnt += (fkey(z[i] / temperature) >= cand) ? 1.f : 0.f;
+      cnt = block_sum_256(cnt, red);
+      if (cnt >= (float)top_k) thr = cand;
+    }
+  }
+  const bool use_p = top_p < 1.0f;
+  double total = 0.0;
+  if (use_p) {
+    for (int i = tid; i < V; i += 256) {
+      const float v = z[i] / temperature;
+      if (fkey(v) >= thr) total += (double)expf(v - mx);
+    }
+    total = block_sum_f64(total);
+  }
+  for (int j = 0; j < m; ++j) {
+    const int id = ids[j];
+    if ((unsigned)id >= (unsigned)V) {
+      if (tid == 0) out[j] = NAN;
+      continue;
+    }
+    const float x = z[id] / temperature;
+    bool keep = fkey(x) >= thr;
+    if (keep && use_p && x < mx) {                    // the row maximum always stays (min_tokens_to_keep = 1)
+      double below = 0.0;                             // kept mass at or below this token = its ascending cumulative mass
+      for (int i = tid; i < V; i += 256) {
+        const float v = z[i] / temperature;
+        if (fkey(v) >= thr && v <= x) below += (double)expf(v - mx);
+      }
+      below = block_sum_f64(below);
+      keep = below > (1.0 - (double)top_p) * total;
+    }
+    if (tid == 0) out[j] = keep ? x : -INFINITY;
+  }
+}
+
 // ---- beam search (HF GenerationMixin._beam_search, do_sample=False, length_penalty=1, early_stopping=False) ------------------------------
 // Candidates of an item are ranked by the accumulated score log_softmax(logits) + beam score, ties to the LOWER flat index beam * V + token.
 // beam_topk: one workgroup per beam row.  The row goes to LDS once; max and log-sum-exp; a 4-level radix select on the monotone key of the
@@ -1004,5 +1089,35 @@ hipError_t launch_sample(const float* logits, int ldl, int rows, int V, float te
   else
     hipLaunchKernelGGL(sample_kernel_generic, dim3(rows), dim3(256), 0, st, logits, ldl, V, 1.0f / temperature, top_k, top_p, seed,
                        step, step_ptr, finished, pad_id, eos_id, out, history);
+  return hipGetLastError();
+}
+
+// Both wrappers check on the host what the kernels index with: rows <= 64, n / m <= OPADPO_MAX_LOGIT_IDS, every id of ids_host (the host copy
+// of the device array ids) inside [0, V), no id twice in a bias table (two threads would add to one address).  Nothing is launched on a refusal.
+static bool logit_ids_ok(const int32_t* ids_host, int n, int V, bool distinct) {
+  for (int i = 0; i < n; ++i) {
+    if (ids_host[i] < 0 || ids_host[i] >= V) return false;
+    if (distinct)
+      for (int j = 0; j < i; ++j)
+        if (ids_host[j] == ids_host[i]) return false;
+  }
+  return true;
+}
+
+hipError_t launch_logit_bias_add(float* logits, int ldl, int rows, int V, const int32_t* ids, const float* bias, const int32_t* ids_host, int n,
+                                 hipStream_t st) {
+  if (n < 0 || n > OPADPO_MAX_LOGIT_IDS || rows < 0 || rows > 64 || V <= 0 || ldl < V) return hipErrorInvalidValue;
+  if (n == 0 || rows == 0) return hipSuccess;
+  if (!logits || !ids || !bias || !ids_host || !logit_ids_ok(ids_host, n, V, true)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(logit_bias_add_kernel, dim3((rows * n + 255) / 256), dim3(256), 0, st, logits, ldl, rows, V, ids, bias, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_scores(const float* logits, int ldl, int rows, int V, const int32_t* ids, const int32_t* ids_host, int m, float temperature,
+                                int top_k, float top_p, float* scores, hipStream_t st) {
+  if (m < 0 || m > OPADPO_MAX_LOGIT_IDS || rows < 0 || rows > 64 || V <= 0 || ldl < V || !(temperature >= 0.f)) return hipErrorInvalidValue;
+  if (m == 0 || rows == 0) return hipSuccess;
+  if (!logits || !ids || !scores || !ids_host || !logit_ids_ok(ids_host, m, V, false)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gather_scores_kernel, dim3(rows), dim3(256), 0, st, logits, ldl, V, ids, m, temperature, top_k, top_p, scores);
   return hipGetLastError();
 }

@@ -223,6 +223,12 @@ hipError_t launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* p_
 hipError_t launch_sample(const float* logits, int ldl, int rows, int V, float temperature, int top_k, float top_p,
                          uint64_t seed, uint64_t step, const int32_t* step_ptr, uint8_t* finished, int pad_id, int eos_id,
                          int32_t* out, int32_t* history, hipStream_t st);
+// logits processors of the yes/no evaluation generator (decode.hip): a sparse additive bias on the fp32 logits of a step, and the processed
+// scores of m token ids.  ids / bias are device arrays, ids_host the host copy of ids that the wrapper checks (range; duplicates in a bias table)
+hipError_t launch_logit_bias_add(float* logits, int ldl, int rows, int V, const int32_t* ids, const float* bias, const int32_t* ids_host, int n,
+                                 hipStream_t st);
+hipError_t launch_gather_scores(const float* logits, int ldl, int rows, int V, const int32_t* ids, const int32_t* ids_host, int m, float temperature,
+                                int top_k, float top_p, float* scores, hipStream_t st);
 hipError_t launch_attn_decode(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, bf16_t* o, const uint8_t* key_mask,
                               int B, int nh, int hd, int ctx, const int32_t* ctx_ptr, int max_ctx, int ldq, float scale,
                               void* workspace, size_t workspace_bytes, hipStream_t st);

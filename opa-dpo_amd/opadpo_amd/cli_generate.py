@@ -5,6 +5,8 @@
     One process per GPU, prompts strided by rank, no collective (replicas only).  The GPT-4V feedback client needs the network
     and stays out of scope: records carry empty feedback fields unless a `feedback` callable is passed to `run_rollout`.
   * `main_eval`     - eval_llava_rlhf_coco/model_vqa.py: question file -> answers JSONL from base weights + a PEFT adapter.
+  * `main_eval_logit` - eval_llava_rlhf_coco/model_vqa_logit.py: the same with a yes/no logit bias (`--logit-bias`) and, with
+    `--output_scores`, the first-token scores of the six yes/no labels instead of answers (POPE-style benchmarks).
 
 `--synthetic tiny|7b` swaps checkpoints, tokenizer and data for random-init stand-ins (no network in the build environment).
 PPO-era / DeepSpeed flags of the reference launchers are accepted and ignored (Quirk Q9).
@@ -71,6 +73,18 @@ def eval_parser() -> argparse.ArgumentParser:
     ap.add_argument("--lora_rank", type=int, default=256)
     ap.add_argument("--lora_alpha", type=float, default=512.0)
     ap.add_argument("--synthetic", default=None, choices=[None, "tiny", "7b"])
+    return ap
+
+
+def eval_logit_parser() -> argparse.ArgumentParser:
+    """eval_parser() plus model_vqa_logit.py:262-263's two flags; `--temperature` defaults to 0.2 as in that script.  The reference declares
+    `--output_scores` with type=bool, which makes every non-empty string - "False" included - true; here it goes through `_bool` like the
+    module's other switches, so `--output_scores False` means false."""
+    ap = eval_parser()
+    ap.description = "evaluation generation with a yes/no logit bias and first-token label scores (MI355X)"
+    ap.set_defaults(temperature=0.2)
+    ap.add_argument("--output_scores", type=_bool, default=False)
+    ap.add_argument("--logit-bias", type=float, default=0)
     return ap
 
 
@@ -171,6 +185,33 @@ def main_eval(argv: Optional[List[str]] = None) -> None:
                          pad_to_square=ns.image_aspect_ratio == "pad", merge_adapter=ns.merge_adapter, batch_size=ns.batch_size,
                          num_beams=ns.num_beams)
     print(f"{n} answers -> {ns.answers_file}")
+
+
+def main_eval_logit(argv: Optional[List[str]] = None) -> None:
+    """model_vqa_logit.py: `--logit-bias b` generates with {Yes: -b, No: +b} added to those tokens' logits at every step; `--output_scores True`
+    writes no answers but one JSON object with the first-token scores of yes / no / Yes / No / \\nYes / \\nNo per question."""
+    from .eval_generate import answer_questions, question_chunk, yes_no_label_ids, yes_no_sequence_bias
+    ns, _ignored = eval_logit_parser().parse_known_args(sys.argv[1:] if argv is None else argv)
+    if ns.num_beams < 1:
+        raise SystemExit(f"--num_beams must be >= 1 (got {ns.num_beams})")
+    if ns.num_beams > 1 and (ns.logit_bias != 0 or ns.output_scores):
+        raise SystemExit(f"--logit-bias / --output_scores are not supported under beam search: --num_beams {ns.num_beams} needs --logit-bias 0 and "
+                         "--output_scores False")
+    if ns.num_beams > 1 and ns.temperature and ns.temperature > 0:
+        raise SystemExit(f"beam sampling is not supported: --num_beams {ns.num_beams} needs --temperature 0 (got {ns.temperature})")
+    if os.path.exists(ns.answers_file):
+        print(f"{ns.answers_file} already exists. Please delete it first.")
+        raise SystemExit(1)
+    engine, adapter, tok = _engine(ns.model_path, ns.synthetic, ns.qlora_path if ns.use_qlora else None, ns.lora_rank, ns.lora_alpha)
+    questions = [json.loads(q) for q in open(os.path.expanduser(ns.question_file), "r")]
+    questions = question_chunk(questions, ns.num_chunks, ns.chunk_idx)
+    n = answer_questions(engine, tok, questions, ns.image_folder, os.path.expanduser(ns.answers_file), adapter=adapter,
+                         model_id=os.path.basename(os.path.normpath(ns.model_path)), temperature=ns.temperature, top_p=ns.top_p,
+                         short_eval=ns.short_eval, test_prompt=ns.test_prompt, image_size=engine.d.image_size,
+                         pad_to_square=ns.image_aspect_ratio == "pad", merge_adapter=ns.merge_adapter, batch_size=ns.batch_size,
+                         num_beams=ns.num_beams, logit_bias=yes_no_sequence_bias(tok, ns.logit_bias) if ns.logit_bias != 0 else None,
+                         score_labels=yes_no_label_ids(tok) if ns.output_scores else None)
+    print(f"{n} {'score rows' if ns.output_scores else 'answers'} -> {ns.answers_file}")
 
 
 if __name__ == "__main__":

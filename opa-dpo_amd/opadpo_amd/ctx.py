@@ -18,7 +18,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence
 
 import torch
 
@@ -275,11 +275,30 @@ class CtxEngine(LlavaEngine):
     @torch.no_grad()
     def generate(self, adapter, queries: torch.Tensor, query_attn_masks: torch.Tensor, image_feats: torch.Tensor, *, max_new_tokens: int,
                  temperature: float, top_k: int, top_p: float, seed: int, eos_token_id: int, pad_token_id: int, suppress_eos: bool,
-                 use_graph: bool) -> torch.Tensor:
+                 use_graph: bool, logit_bias: Optional[Dict[int, float]] = None, score_ids: Optional[Sequence[int]] = None):
         """-> responses [B, max_new_tokens] int64 (pad after a row finished); prefill, KV cache and the per-token launch loop (or hipGraph) live in
-        the context (opadpo_decode_begin / opadpo_decode_run)."""
+        the context (opadpo_decode_begin / opadpo_decode_run).
+        logit_bias {token id: bias}: added to that token's logit in every row at every step, before temperature / top-k / top-p (HF
+        `sequence_bias` with one-token sequences; at most 64 entries).  An empty dict is no bias: the launches of a call without the keyword.
+        score_ids (at most 64 token ids, repeats allowed): the return value becomes (responses, scores [B, len(score_ids)] fp32), the
+        PROCESSED scores of the first generated token as HF's `generate(output_scores=True).scores[0]` holds them -
+        (logit + bias) / temperature, then the top-k / top-p cuts (a cut token reads -inf).
+        temperature == 0 means greedy decoding here (HF refuses do_sample=True with temperature 0; this tree's evaluation path treats 0 as
+        greedy and runs it as top_k = 1): the scores are then logit + bias, nothing divided and nothing cut."""
         dev, d = self.dev, self.d
         B, Q = queries.shape
+        greedy = temperature == 0
+        if greedy:
+            temperature, top_k, top_p = 1.0, 1, 1.0
+        bias = {int(k): float(v) for k, v in (logit_bias or {}).items()}
+        sids = None if score_ids is None else [int(t) for t in score_ids]
+        scores = None
+        if bias or sids is not None:
+            if len(bias) > 64 or len(sids or ()) > 64:
+                raise ValueError("at most 64 logit_bias entries and 64 score_ids")
+            bad = [t for t in list(bias) + (sids or []) if not 0 <= t < d.vocab]
+            if bad:
+                raise ValueError(f"token ids outside [0, {d.vocab}): {bad}")
         self._ensure_rope(Q + d.n_patches - 1 + max_new_tokens)
         slot = self.adapter_slot(adapter)
         ids = queries.to(dev).to(torch.int32).contiguous()
@@ -287,9 +306,16 @@ class CtxEngine(LlavaEngine):
         feats = image_feats.contiguous()
         history = torch.empty(max_new_tokens, B, dtype=torch.int32, device=dev)
         st = L.stream()
-        self._call("opadpo_decode_begin", slot, _ptr(ids), _ptr(tmask), _ptr(feats), B, Q, int(max_new_tokens), float(temperature), int(top_k),
-                   float(top_p), int(seed), int(eos_token_id), int(pad_token_id), int(suppress_eos), _ptr(history), st)
+        if bias or sids:
+            n, m = len(bias), len(sids or ())
+            scores = torch.empty(B, m, dtype=torch.float32, device=dev) if m else None
+            self._call("opadpo_ctx_set_logit_processors", (C.c_int32 * n)(*bias.keys()), (C.c_float * n)(*bias.values()), n,
+                       (C.c_int32 * m)(*(sids or ())), m, _ptr(scores), int(greedy))
+        elif sids is not None:
+            scores = torch.empty(B, 0, dtype=torch.float32, device=dev)
         try:
+            self._call("opadpo_decode_begin", slot, _ptr(ids), _ptr(tmask), _ptr(feats), B, Q, int(max_new_tokens), float(temperature), int(top_k),
+                       float(top_p), int(seed), int(eos_token_id), int(pad_token_id), int(suppress_eos), _ptr(history), st)
             left = max_new_tokens - 1
             fin = C.c_int(0)
             while left > 0:
@@ -303,14 +329,18 @@ class CtxEngine(LlavaEngine):
             torch.cuda.current_stream().synchronize()
         finally:
             self._call("opadpo_decode_end")
-        return history.t().contiguous().to(torch.int64)
+        tokens = history.t().contiguous().to(torch.int64)
+        return tokens if score_ids is None else (tokens, scores)
 
     @torch.no_grad()
     def generate_beams(self, adapter, queries: torch.Tensor, query_attn_masks: torch.Tensor, image_feats: torch.Tensor, *, num_beams: int,
-                       max_new_tokens: int, eos_token_id: int, pad_token_id: int, use_graph: bool):
+                       max_new_tokens: int, eos_token_id: int, pad_token_id: int, use_graph: bool, logit_bias=None, score_ids=None):
         """Beam search (HF generate(num_beams=k, do_sample=False, length_penalty=1.0, early_stopping=False)) -> (tokens [B, max_new_tokens]
         int64 with EOS kept and pad after it, scores [B] fp32 = sum of token log-probabilities / generated length).  One prefill per query;
         selection, backpointers and the KV slot table stay on the device (opadpo_decode_beam_begin / opadpo_decode_run / _beam_result)."""
+        if logit_bias or score_ids is not None:
+            raise NotImplementedError("logit_bias / score_ids are not supported under beam search: the context engine (CtxEngine.generate) applies "
+                                      "them to the sampling / greedy rollout only")
         dev, d = self.dev, self.d
         B, Q = queries.shape
         k = int(num_beams)

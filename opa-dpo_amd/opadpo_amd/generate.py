@@ -12,7 +12,7 @@ the new token of every row sits at the same position: one RoPE position and one 
 from __future__ import annotations
 
 import types
-from typing import List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -73,23 +73,34 @@ class Generator:
     def generate(self, queries: torch.Tensor, query_attn_masks: torch.Tensor, images: Optional[torch.Tensor] = None, *,
                  image_feats: Optional[torch.Tensor] = None, max_new_tokens: int, temperature: float = 1.0, top_k: int = 0,
                  top_p: float = 1.0, seed: int = 0, eos_token_id: int = EOS_ID, pad_token_id: int = PAD_ID,
-                 suppress_eos: bool = False, num_beams: int = 1) -> torch.Tensor:
+                 suppress_eos: bool = False, num_beams: int = 1, logit_bias: Optional[Dict[int, float]] = None,
+                 score_ids: Optional[Sequence[int]] = None):
         """-> responses [B, max_new_tokens] int64 (pad after a row finished).  num_beams > 1: beam search (HF num_beams, do_sample=False;
-        temperature / top_k / top_p / seed are not used), the best hypothesis per query."""
+        temperature / top_k / top_p / seed are not used), the best hypothesis per query.
+        logit_bias / score_ids (context engine only; ctx.CtxEngine.generate documents them): an additive bias on single tokens' logits at every
+        step, and the first generated token's processed scores at score_ids - the return value is then (responses, scores [B, m])."""
         eng, d, b = self.engine, self.engine.d, self.engine.base
         dev = eng.dev
+        if logit_bias or score_ids is not None:
+            if not hasattr(eng, "ctx"):
+                raise NotImplementedError("logit_bias / score_ids run on the context engine (CtxEngine) only: the sampler of the op-level LlavaEngine "
+                                          "path is a cross-check of the sampling rollout")
+            if num_beams > 1:
+                raise NotImplementedError("logit_bias / score_ids are not supported under beam search (CtxEngine.generate_beams); the context engine "
+                                          "applies them to the sampling / greedy rollout (num_beams = 1)")
         if num_beams > 1 and not hasattr(eng, "ctx"):
             raise NotImplementedError("beam search runs on the context engine (CtxEngine) only; the op-level LlavaEngine path is a cross-check of "
                                       "the sampling rollout")
         if hasattr(eng, "ctx"):      # CtxEngine: prefill, KV cache, the per-token launch loop (optionally a hipGraph) and the sampler live below the C ABI
             if image_feats is None:
                 image_feats = eng.encode_images(images)
+            extra = {} if not logit_bias and score_ids is None else dict(logit_bias=logit_bias, score_ids=score_ids)
             if num_beams > 1:
                 return eng.generate_beams(self.adapter, queries, query_attn_masks, image_feats, num_beams=num_beams, max_new_tokens=max_new_tokens,
                                           eos_token_id=eos_token_id, pad_token_id=pad_token_id, use_graph=self.use_graph)[0]
             return eng.generate(self.adapter, queries, query_attn_masks, image_feats, max_new_tokens=max_new_tokens, temperature=temperature,
                                 top_k=top_k, top_p=top_p, seed=seed, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                                suppress_eos=suppress_eos, use_graph=self.use_graph)
+                                suppress_eos=suppress_eos, use_graph=self.use_graph, **extra)
         # op-level sequencing of the same kernels (LlavaEngine): kept as the cross-check of the context path (tests/test_ctx_gpu.py)
         st = L.stream()
         B, Q = queries.shape
