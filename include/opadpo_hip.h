@@ -448,6 +448,13 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* ctx, opadpo_saved* saved, const float* d
  * decoder layer), hashed with the pass's own row numbers; no-grad passes (train = 0), merged adapters, prefill and decode never apply dropout.  p = 0 is
  * the pass without this call: the same launches, buffers and bits. */
 int opadpo_ctx_set_lora_dropout(opadpo_ctx* ctx, double p, uint64_t seed, uint64_t call);
+/* Gradient checkpointing (HF gradient_checkpointing_enable(): recompute every decoder layer in the backward) of the TRAINING forwards of this context,
+ * on != 0 until switched off again; default off.  A checkpointed forward keeps the fp32 residual stream x_0 .. x_{n_layers}, the key mask, the row
+ * geometry, the head buffers and the dropout descriptor, and ONE layer's activation slot instead of n_layers of them (what a no-grad pass holds);
+ * the handle remembers the mode.  opadpo_seq_logprobs_bwd re-runs layer i's forward from x_i into that slot - without the down projection's base
+ * product, whose result nothing reads - right before layer i's backward, ranged calls included.  Every kernel of the forward is deterministic, so
+ * log-probs, entropies and LoRA gradients carry the bits of the resident pass.  No-grad passes (train = 0) are unaffected. */
+int opadpo_ctx_set_grad_checkpoint(opadpo_ctx* ctx, int on);
 int opadpo_saved_release(opadpo_ctx* ctx, opadpo_saved* saved);
 /* diagnostics (parity tests: the per-layer drift curve of the residual stream): copies the fp32 residual stream ENTERING decoder
  * layer `layer` of a training forward, [rows, hidden], into dst (device memory, rows*hidden floats) and returns the row count in

@@ -199,7 +199,9 @@ struct opadpo_saved {
   int S = 0, L = 0, T = 0, K = 1, M = 0, R = 0, n_txt = 0, train = 0, adapter = -1;
   int seg_prefix = 0, seg_len = 0;
   float temperature = 1.f;
-  int nb = 1;                       // per-layer activation slots (n_layers when train, 1 otherwise)
+  int nb = 1;                       // per-layer activation slots (n_layers for a resident training pass, 1 otherwise)
+  int ckpt = 0;                     // gradient checkpointing (opadpo_ctx_set_grad_checkpoint; training passes only): ONE slot, the backward re-runs a layer's
+                                    // forward from the kept x_i into it before that layer's backward
   float* x = nullptr;               // [(nl+1) or 2][M,H] fp32 residual stream
   bf16_t *n1, *qkv, *t_qkv, *attn, *t_o, *n2, *t_gu, *gu, *act, *t_d;
   float *rstd1, *rstd2, *lse, *h;
@@ -246,10 +248,12 @@ struct opadpo_ctx {
   void* ws = nullptr; size_t ws_bytes = 0;        // scratch of vision / backward / decode
   void* gemm_ws = nullptr; size_t gemm_ws_bytes = 0;      // partial sums of the K-folded gemm_nt products (run_gemm; never c->ws, which passes carve around it)
   size_t bytes_live = 0, bytes_peak = 0;
-  size_t arena_hint[2][16] = {};                  // largest activation arena requested so far, per (no-grad / training pass, responses per row K):
-                                                  // CoPO's K = 2 masked pass does not inherit the K = 3 pass's worst case
+  size_t arena_hint[3][16] = {};                  // largest activation arena requested so far, per (no-grad / resident training / checkpointed training pass,
+                                                  // responses per row K): CoPO's K = 2 masked pass does not inherit the K = 3 pass's worst case, a checkpointed
+                                                  // pass not a resident one's n_layers slots
   std::vector<opadpo_saved*> live;
   bool next_drop_on = false; LoraDropout next_drop{};      // opadpo_ctx_set_lora_dropout: consumed by the next training forward
+  bool grad_checkpoint = false;                   // opadpo_ctx_set_grad_checkpoint: read by every training forward, remembered in its opadpo_saved
   // opadpo_ctx_set_logit_processors: host copies, read by the next opadpo_decode_begin and cleared by opadpo_decode_end
   struct LogitArm { std::vector<int32_t> bias_ids, score_ids; std::vector<float> bias; float* scores = nullptr; int raw = 0; } next_logit;
   // dispatch: opadpo_ctx_set_flags(gemm_variant, use_tr), parsed once; the use_tr bits below are off for a negative word
@@ -451,7 +455,7 @@ struct DropFwd { LoraDropout dp; bf16_t* xm; };
 // GEMM whatever K, profiles/r05m_resid_probe_k.txt), so the add lives in the projections again and this form is the A/B switch (context flag bit 13).
 // ydef == nullptr (decode steps: a few rows; fused-residual full-sequence passes): residual in the epilogue, result in xo.
 hipError_t mlp_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const float* h, float* xo, const LayerBufs& b, int M, int stream_hint, hipStream_t st,
-                   float* ydef = nullptr, bool norm_done = false, const DropFwd* dr = nullptr, const int32_t* drop_rows = nullptr) {
+                   float* ydef = nullptr, bool norm_done = false, const DropFwd* dr = nullptr, const int32_t* drop_rows = nullptr, bool recompute = false) {
   const opadpo_dims& d = c->d;
   const int H = d.hidden, F = d.ffn, r = d.lora_r;
   const float s = d.lora_alpha / d.lora_r;
@@ -488,10 +492,12 @@ hipError_t mlp_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const fl
       g3.A1 = dr->xm;
     }
     if ((e = run_gemm(c, g3, st)) != hipSuccess) return e;
+    if (recompute) return hipSuccess;               // t_d is the last thing the backward reads: no down product, nothing written to xo / ydef
     GemmNTArgs g4 = gemm(b.act, F, w.wd, F, F, ydef ? ydef : xo, H, 1, M, H); tail(g4, b.t_d, r, lw + o.b_d, r, r); g4.act |= stream_hint;
     if (!ydef) resid(g4, h, H, 1);
     return run_gemm(c, g4, st);
   }
+  if (recompute) return hipSuccess;
   GemmNTArgs g4 = gemm(b.act, F, w.wd, F, F, ydef ? ydef : xo, H, 1, M, H); g4.act |= stream_hint;
   if (!ydef) resid(g4, h, H, 1);
   return run_gemm(c, g4, st);
@@ -504,9 +510,12 @@ struct TopRows { const int32_t* urow; int n; bf16_t* attn_u; float* x_u; };
 // Input of the layer: x = res (+ yin when yin != nullptr: the previous layer's down-projection product, residual deferred).  x is written
 // to `x` (may alias res when yin is null), the layer leaves h = x + attention branch in b.h and its own down-projection product in Y:
 // the caller hands (b.h, Y) to the next layer / the final norm.
+// recompute (backward of a checkpointed pass): the layer is re-run from its kept input x (= res, yin null) up to what the backward reads - b.* through t_d;
+// the down projection's base product is skipped and the layer's output is NOT written.  Y is then scratch of the deferred-residual form only (the o
+// projection's product; may be null with the fused residual).
 hipError_t layer_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const float* res, const float* yin, float* x, float* Y, const LayerBufs& b, int S, int Lp,
                      const uint8_t* key_mask, int seg0, int seg1, bf16_t* kc, bf16_t* vc, int max_ctx, hipStream_t st, const Rag* rg = nullptr,
-                     const TopRows* top = nullptr, const DropFwd* dr = nullptr) {
+                     const TopRows* top = nullptr, const DropFwd* dr = nullptr, bool recompute = false) {
   const opadpo_dims& d = c->d;
   const int H = d.hidden, r = d.lora_r, nh = d.n_heads, hd = d.head_dim;
   if (dr && !lw_kind1(ad)) dr = nullptr;            // dropout belongs to the LoRA branch
@@ -590,10 +599,10 @@ hipError_t layer_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const 
   }
   if (fr) {
     if ((e = launch_rmsnorm_fwd(b.h, 1, w0.ln2, b.n2, b.rstd2, Mo, H, d.rms_eps, st)) != hipSuccess) return e;      // n2 = norm(h)
-    return mlp_fwd(c, i, ad, b.h, Y, b, Mo, 0, st, nullptr, true, dr, top ? top->urow : nullptr);                   // Y = h + down(..)
+    return mlp_fwd(c, i, ad, b.h, Y, b, Mo, 0, st, nullptr, true, dr, top ? top->urow : nullptr, recompute);        // Y = h + down(..)
   }
   if ((e = launch_rmsnorm_sum_fwd(xr, 1, Y, 1, (size_t)Mo * H, w0.ln2, b.h, b.n2, b.rstd2, Mo, H, d.rms_eps, st)) != hipSuccess) return e;      // h = x + attn . Wo, n2 = norm(h)
-  return mlp_fwd(c, i, ad, b.h, nullptr, b, Mo, 0, st, Y, true, dr, top ? top->urow : nullptr);
+  return mlp_fwd(c, i, ad, b.h, nullptr, b, Mo, 0, st, Y, true, dr, top ? top->urow : nullptr, recompute);
 }
 
 size_t saved_layout(const opadpo_dims& d, opadpo_saved* sv, void* base) {
@@ -720,6 +729,12 @@ int opadpo_ctx_set_lora_dropout(opadpo_ctx* c, double p, uint64_t seed, uint64_t
   LoraDropout dp;
   if (lora_dropout_make(p, seed, call, &dp)) return cbad(c, __func__, "need 0 <= p < 1 and seed < 2^32");
   c->next_drop = dp; c->next_drop_on = true;
+  return 0;
+}
+
+int opadpo_ctx_set_grad_checkpoint(opadpo_ctx* c, int on) {
+  if (!c) return (int)hipErrorInvalidValue;
+  c->grad_checkpoint = on != 0;
   return 0;
 }
 
@@ -902,7 +917,9 @@ int opadpo_seq_logprobs_fwd(opadpo_ctx* c, int adapter_id, const int32_t* ids, c
   opadpo_saved* sv = new (std::nothrow) opadpo_saved();
   if (!sv) return cfail(c, hipErrorOutOfMemory, __func__);
   sv->S = S; sv->L = Lp; sv->T = T; sv->K = K; sv->M = S * Lp; sv->R = K * S * T; sv->n_txt = n_txt; sv->train = train ? 1 : 0;
-  sv->adapter = adapter_id; sv->temperature = temperature; sv->nb = train ? d.n_layers : 1;
+  sv->adapter = adapter_id; sv->temperature = temperature;
+  sv->ckpt = train && c->grad_checkpoint ? 1 : 0;
+  sv->nb = train && !sv->ckpt ? d.n_layers : 1;
   const int pfx = Lp - K * T;
   sv->seg_prefix = K > 1 ? pfx : 0; sv->seg_len = K > 1 ? T : 0;
   sv->ids = ids; sv->feat_row = feat_row;
@@ -959,7 +976,7 @@ int opadpo_seq_logprobs_fwd(opadpo_ctx* c, int adapter_id, const int32_t* ids, c
   sv->bytes = saved_layout(d, sv, nullptr);
   // ragged batches differ in size: ask for the largest arena seen so far for this kind of pass, so that the allocator hands the
   // same block back every time instead of growing (and fragmenting) its pool
-  size_t& hint = c->arena_hint[train ? 1 : 0][std::min(K, 15)];
+  size_t& hint = c->arena_hint[train ? 1 + sv->ckpt : 0][std::min(K, 15)];
   if (sv->ragged) {                               // size for the padded row count of this shape: a ragged batch can never need more
     opadpo_saved worst = *sv;
     worst.M = S * Lp; worst.L = Lp;
@@ -1011,7 +1028,7 @@ int opadpo_seq_logprobs_fwd(opadpo_ctx* c, int adapter_id, const int32_t* ids, c
   const bool fr = !c->resid_deferred;
   const DropFwd drop_fwd{sv->drop, sv->xm};
   for (int i = 0; i < d.n_layers; ++i) {
-    const LayerBufs lb = slot(d, sv, train ? i : 0);
+    const LayerBufs lb = slot(d, sv, sv->nb > 1 ? i : 0);
     float* x = sv->x + (size_t)(train ? i : (i & 1)) * MH;
     // fused residual: the layer writes its OUTPUT x_{i+1} = h + down(..) into the next layer's slot (training: slot i + 1, the last one being the
     // old branch-product slot; no-grad: the other of the two alternating slots)
@@ -1124,7 +1141,8 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
     cv.take<float>(MH); cv.take<bf16_t>(MH); cv.take<bf16_t>(MH); cv.take<bf16_t>((size_t)M * F); cv.take<bf16_t>((size_t)M * 2 * F); cv.take<bf16_t>(MH);
     cv.take<bf16_t>((size_t)M * 3 * H); cv.take<float>((size_t)S * nh * Lp); cv.take<bf16_t>((size_t)M * r); cv.take<bf16_t>((size_t)M * 2 * r);
     cv.take<bf16_t>((size_t)M * 3 * r); cv.take<bf16_t>((size_t)M * r); cv.take<float>(sv->Uc > 0 ? MH : 1); cv.take<float>(tn_ws_floats);
-    cv.take<bf16_t>(sv->drop_on ? (size_t)M * (F + 6 * H) : 0); cv.take<bf16_t>(sv->drop_on ? (size_t)M * std::max(3 * H, F) : 0); need = cv.off; }
+    cv.take<bf16_t>(sv->drop_on ? (size_t)M * (F + 6 * H) : 0); cv.take<bf16_t>(sv->drop_on ? (size_t)M * std::max(3 * H, F) : 0);
+    cv.take<float>(sv->ckpt && sv->Uc > 0 ? (size_t)sv->Uc * H : 1); cv.take<float>(sv->ckpt && c->resid_deferred ? MH : 1); need = cv.off; }
   const bool first = layer_hi == d.n_layers - 1;
   if (first) c->wgrad_det = 1;                        // of THIS backward: cleared below by any grouped wgrad launch that fell back to fp32 atomics
   if (R == 0) return 0;                               // no valid response token: every gradient of this pass is exactly zero (nothing flushed: trivially reproducible)
@@ -1147,8 +1165,15 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
   bf16_t* xm_d = cv.take<bf16_t>(drop ? (size_t)M * (F + 6 * H) : 0);
   bf16_t* xm_gu = xm_d + (size_t)M * F; bf16_t* xm_o = xm_gu + (size_t)M * 2 * H; bf16_t* xm_qkv = xm_o + MH;
   bf16_t* du = cv.take<bf16_t>(drop ? (size_t)M * std::max(3 * H, F) : 0);
+  // checkpointed pass: scratch of the recomputed layers - the gathered input of the compact top layer (the forward borrowed sv->hs, which the head
+  // backward owns by now) and, deferred-residual form only, the o projection's product.  Never a kept x slot.
+  float* rc_xu = cv.take<float>(sv->ckpt && sv->Uc > 0 ? (size_t)sv->Uc * H : 1);
+  float* rc_y = cv.take<float>(sv->ckpt && c->resid_deferred ? MH : 1);
   const LoraDropout& dp = sv->drop;
   const LoraOff o = lora_off(d);
+  const Rag rag{sv->meta, sv->meta_stride, sv->K, M, sv->row_pos};
+  const TopRows top_rc{sv->urow, sv->Uc, sv->attn_u, rc_xu};
+  const DropFwd drop_rc{sv->drop, sv->xm};
   if (first) {
     if (!dlogp) return cbad(c, __func__, "null dlogp");
     if (sv->ragged && R > 0) {      // gradients of the compact head rows: gathered from the rectangular [K,S,T] gradients (into d_hs, free until the norm backward)
@@ -1185,7 +1210,13 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
     if (!w.wqkv_t || !w.wo_t || !w.wgu_t || !w.wd_t) return cbad(c, __func__, "transposed base weights not set (needed by dgrad)");
     const bf16_t* wt = ad.work_t + (size_t)i * o.layer;
     float* gr = ad.grad + (size_t)i * o.layer;
-    const LayerBufs b = slot(d, sv, i);
+    const LayerBufs b = slot(d, sv, sv->ckpt ? 0 : i);
+    if (sv->ckpt) {                                 // the slot holds whatever layer ran last: re-run layer i from x_i with the forward's arguments
+      float* const xi = sv->x + (size_t)i * MH;
+      hipError_t e = layer_fwd(c, i, ad, xi, nullptr, xi, c->resid_deferred ? rc_y : nullptr, b, S, Lp, sv->key_mask, sv->seg_prefix, sv->seg_len, nullptr, nullptr, 0,
+                               st, sv->ragged ? &rag : nullptr, (sv->Uc > 0 && i == d.n_layers - 1) ? &top_rc : nullptr, drop ? &drop_rc : nullptr, true);
+      if (e != hipSuccess) return cfail(c, e, "opadpo_seq_logprobs_bwd (layer recompute)");
+    }
     // the 8 LoRA wgrads of the layer are collected and run as ONE grouped launch (launch_gemm_tn_group) once the last of their
     // operands exists: every operand stays untouched until then (dt_ra is the second dT buffer that makes that true)
     GemmTNArgs wg[8];

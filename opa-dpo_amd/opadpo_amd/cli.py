@@ -44,6 +44,7 @@ FLAGS = [
     ("mm_use_im_start_end", "st", None), ("mm_use_im_patch_token", "st", None), ("freeze_mm_mlp_adapter", "st", None),
     # additions of this build
     ("optimizer_mode", str, "zero1"), ("synthetic", str, None), ("merge_ref_adapter", int, 0),
+    ("gradient_checkpointing", "sbool", "False"),
 ]
 
 

@@ -152,6 +152,14 @@ class CtxEngine(LlavaEngine):
         """Kernel-variant switches of THIS context (lib.set_flags documents the values); -1 = process default."""
         self._call("opadpo_ctx_set_flags", int(gemm_variant), int(use_tr))
 
+    def set_grad_checkpoint(self, on: bool) -> None:
+        """Gradient checkpointing of the training forwards of this context (opadpo_ctx_set_grad_checkpoint): a training pass keeps the residual stream
+        and ONE layer's activations, the backward re-runs each decoder layer's forward before its backward.  Same bits, (n_layers - 1) activation
+        slots less, about one forward without embedding, head and down product more.  No-grad passes are unaffected."""
+        if bool(on) != getattr(self, "_grad_checkpoint", False):      # policies set it before every training forward: one C call per change
+            self._call("opadpo_ctx_set_grad_checkpoint", int(bool(on)))
+            self._grad_checkpoint = bool(on)
+
     def profile(self, enable: bool) -> None:
         """Bracket every gemm_nt launch of the context with HIP events on the launch stream (bench.py roofline record)."""
         self._call("opadpo_ctx_profile", int(enable))

@@ -91,6 +91,7 @@ SIGNATURES.update({
     "opadpo_seq_logprobs_fwd": [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p],
     "opadpo_seq_logprobs_bwd": [_p, _p, _p, _p, _p, _i, _i, _p],
     "opadpo_ctx_set_lora_dropout": [_p, _d, _u64, _u64],
+    "opadpo_ctx_set_grad_checkpoint": [_p, _i],
     "opadpo_saved_release": [_p, _p],
     "opadpo_saved_residual": [_p, _p, _i, _p, _p, _p],
     "opadpo_ctx_set_logit_processors": [_p, _p, _p, _i, _p, _i, _p, _i],

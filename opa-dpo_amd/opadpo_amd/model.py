@@ -316,6 +316,11 @@ class LlavaEngine:
     def release(self) -> None:
         self._ws.clear()
 
+    def set_grad_checkpoint(self, on: bool) -> None:
+        if on:
+            raise NotImplementedError("gradient checkpointing runs on the context engine (CtxEngine) only: the op-level LlavaEngine keeps every layer's "
+                                      "activations resident")
+
     # -- vision: CLIP-ViT hidden_states[-2][:,1:] -> mlp2x_gelu ------------------------------------------
     @torch.no_grad()
     def encode_images(self, pixels: torch.Tensor) -> torch.Tensor:

@@ -48,6 +48,7 @@ def host_row_plan(queries: torch.Tensor, queries_attn_masks: torch.Tensor, respo
 class _SeqLogprobs(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, policy, batch, feats, temperature):
+        policy.engine.set_grad_checkpoint(policy.gradient_checkpointing)      # the engine is shared: the switch is this policy's for this forward
         logp, ent, saved = policy.engine.seq_logprobs_fwd(policy.adapter, batch, feats, temperature, train=True, **policy.next_dropout())
         ctx.policy, ctx.saved = policy, saved
         policy._pending_bwd += 1
@@ -88,12 +89,19 @@ class AutoregressivePolicy(torch.nn.Module):
         # micro-batches or ranks share masks; the trainer saves / restores the counter with its checkpoints.
         self.lora_dropout, self.dropout_seed, self.dropout_calls = 0.0, 0, 0
         self.dropout_rank, self.dropout_world = 0, 1
+        # gradient checkpointing (--gradient_checkpointing): the TRAINING forward keeps one layer's activations, the backward recomputes each layer;
+        # same log-probs and gradients bit for bit.  No-grad passes (reference policy, rollouts) hold one slot anyway.
+        self.gradient_checkpointing = False
         self.layer_done_hook = None       # callable(layer) set by the trainer on the gradient-sync micro-batch (optim.launch_bucket)
 
     def set_lora_dropout(self, rate: float, seed: int = 0, rank: int = 0, world: int = 1) -> None:
         if not 0.0 <= rate < 1.0:
             raise ValueError(f"lora_dropout must be in [0, 1), got {rate}")
         self.lora_dropout, self.dropout_seed, self.dropout_rank, self.dropout_world = float(rate), int(seed), int(rank), int(world)
+
+    def set_gradient_checkpointing(self, on: bool) -> None:
+        self.engine.set_grad_checkpoint(bool(on))         # an engine without it (op-level LlavaEngine) refuses here, not in the first step
+        self.gradient_checkpointing = bool(on)
 
     def next_dropout(self) -> dict:
         """Keyword arguments of engine.seq_logprobs_fwd for the next training forward (empty at rate 0: the call is the one without dropout)."""

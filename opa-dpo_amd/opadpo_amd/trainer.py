@@ -117,6 +117,9 @@ class DPOTrainer:
         # --lora_drop: dropout on the policy's TRAINING forward only (compute_policy_loss); rollout() runs under no_grad and the reference policy is frozen
         self.lora_dropout = float(getattr(args, "lora_drop", 0.0) or 0.0)
         policy.set_lora_dropout(self.lora_dropout, getattr(args, "seed", 42), self.rank, self.world)
+        # --gradient_checkpointing: recompute in the backward of the policy's training forwards (compute_policy_loss, the CoPO masked pass included)
+        self.gradient_checkpointing = bool(getattr(args, "gradient_checkpointing", False))
+        policy.set_gradient_checkpointing(self.gradient_checkpointing)
         self.sched_step = 0
         self.total_sched_steps = 1
         self.log_history: List[dict] = []
