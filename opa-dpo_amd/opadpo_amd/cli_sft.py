@@ -2,7 +2,8 @@
 reference (LoRA tuning of LLM + CLIP tower + projector: LORATUNE=True, TUNE_MM_PROJECT / TUNE_BASE_MODEL / TUNE_VISION_TOWER
 = True, rank 256 / alpha 512, per-device batch 4 x 8 accumulation steps, 2 epochs, entropy regulariser off).  DeepSpeed /
 tf32 / flash-attention switches are accepted and ignored (one process per GPU over RCCL, flat-gradient exchange per
-optimizer step like the DPO stage); full fine-tuning (`--full_tune True`) is not built.  `--cfg` is read with PyYAML and only
+optimizer step like the DPO stage); `--gradient_checkpointing True` (the reference's `gradient_checkpointing: True`, honoured from
+`--cfg` too) recomputes every decoder layer and every CLIP layer in the backward, same bits; full fine-tuning (`--full_tune True`) is not built.  `--cfg` is read with PyYAML and only
 fills values the command line did not set.  Output: `<output_dir>/checkpoint-final/adapter_model.bin` (+ adapter_config.json),
 the adapter the DPO stage starts from.
 """
@@ -29,6 +30,7 @@ FLAGS = [
     ("image_aspect_ratio", str, "pad"), ("max_steps", int, -1),
     # additions of this build
     ("optimizer_mode", str, "zero1"), ("synthetic", str, None), ("synthetic_samples", int, 64),
+    ("gradient_checkpointing", "sbool", "False"),
 ]
 
 
@@ -44,8 +46,8 @@ def make_parser() -> argparse.ArgumentParser:
     return p
 
 
-def main(argv: Optional[List[str]] = None) -> None:
-    argv = sys.argv[1:] if argv is None else argv
+def parse_args(argv: List[str]) -> argparse.Namespace:
+    """Command line, then `--cfg` for what it left unset, then the recipe checks; needs no device."""
     ns = make_parser().parse_args(argv)
     from .cli import _as_bool, load_yaml_defaults
     load_yaml_defaults(ns, argv)
@@ -60,6 +62,12 @@ def main(argv: Optional[List[str]] = None) -> None:
         raise SystemExit("only the LoRA recipe of run/train_opa.sh is built (lora_tune True, full_tune False)")
     if not (ns.tune_mm_mlp_adapter and ns.tune_base_model and ns.tune_vision_tower):
         raise SystemExit("the LoRA recipe tunes projector, LLM and vision tower together (TUNE_* = True in run/train_opa.sh)")
+    return ns
+
+
+def main(argv: Optional[List[str]] = None) -> None:
+    argv = sys.argv[1:] if argv is None else argv
+    ns = parse_args(argv)
     import torch
     import torch.distributed as dist
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
@@ -118,7 +126,10 @@ def main(argv: Optional[List[str]] = None) -> None:
                     lr=ns.learning_rate, max_grad_norm=ns.max_grad_norm, weight_decay=ns.weight_decay, optimizer_mode=ns.optimizer_mode,
                     entropy_loss=ns.entropy_loss, entropy_mask_ratio=ns.entropy_mask_ratio, entropy_mask_method=ns.entropy_mask_method,
                     entropy_loss_coef=ns.entropy_loss_coef, entropy_decay_coef=ns.entropy_decay_coef, lora_dropout=ns.lora_drop, seed=ns.seed,
-                    rank=rank, world=world)
+                    rank=rank, world=world, gradient_checkpointing=ns.gradient_checkpointing)
+    if rank == 0:
+        print("gradient checkpointing on: the backward recomputes every decoder layer and every CLIP layer" if ns.gradient_checkpointing
+              else "gradient checkpointing off: every layer's activations stay resident", flush=True)
     total = int(math.ceil(ns.num_train_epochs * steps_per_epoch)) if ns.max_steps <= 0 else ns.max_steps
     warm = int(math.ceil(ns.warmup_ratio * total))
     step, micro, log = 0, 0, []

@@ -42,8 +42,14 @@ class SFTTrainer:
                  lr: float = 2e-5, max_grad_norm: Optional[float] = 1.0, weight_decay: float = 0.0, optimizer_mode: str = "allreduce",
                  entropy_loss: bool = False, entropy_mask_ratio: float = 0.2, entropy_mask_method: str = "random",
                  entropy_loss_coef: float = 1.0, entropy_decay_coef: float = 1.0, lora_dropout: float = 0.0, seed: int = 0, rank: int = 0,
-                 world: int = 1):
+                 world: int = 1, gradient_checkpointing: bool = False):
         assert llm_adapter.trainable
+        # --gradient_checkpointing: both training forwards of a micro-batch (CE and the entropy pass) keep one decoder layer's and one CLIP layer's
+        # activations; the backwards recompute layer by layer.  Same loss and gradients bit for bit.  An engine without the switch (op-level
+        # LlavaEngine) refuses here, not in the first step.
+        self.gradient_checkpointing = bool(gradient_checkpointing)
+        engine.set_grad_checkpoint(self.gradient_checkpointing)
+        self.layer_done_hook = None       # callable(layer): fired by the LAST LLM backward of a micro-batch once that layer's LLM LoRA gradient is final
         self.entropy_loss, self.entropy_mask_ratio, self.entropy_mask_method = entropy_loss, entropy_mask_ratio, entropy_mask_method
         self.entropy_loss_coef, self.entropy_decay_coef = entropy_loss_coef, entropy_decay_coef
         self.last = {}
@@ -67,7 +73,9 @@ class SFTTrainer:
         _, batch = self._policy.build_batch(queries, queries_attn_masks, {"response": responses})
         mask = (responses.to(dev) != PAD_ID)
         n = mask.sum().clamp_min(1).float()
-        feats, vsv = self.vision.forward(images)
+        ck = self.gradient_checkpointing
+        eng.set_grad_checkpoint(ck)      # the engine is shared: the switch is this trainer's for the training forwards of this call
+        feats, vsv = self.vision.forward(images, checkpoint=ck)
         logp, ent, sv = eng.seq_logprobs_fwd(self.llm, batch, feats.view(B, d.n_patches, d.hidden), 1.0, train=True, **self._policy.next_dropout())
         loss = -(logp * mask).sum() / n
         self.last = {"base_sft_loss": float(loss), "mask_sft_loss": 0.0, "entropy_loss": 0.0}
@@ -89,7 +97,7 @@ class SFTTrainer:
                     masked_images = torch.stack([mask_single_image(images[i].unsqueeze(0).cpu(), self.entropy_mask_ratio,
                                                                    self.entropy_mask_method) for i in range(B)]).squeeze(1)
                 batch2 = batch
-                feats2, vsv2 = self.vision.forward(masked_images)
+                feats2, vsv2 = self.vision.forward(masked_images, checkpoint=ck)
                 d_feats2 = torch.zeros(B, d.n_patches, d.hidden, dtype=torch.float32, device=dev)
             logp2, ent2, sv2 = eng.seq_logprobs_fwd(self.llm, batch2, feats2.view(B, d.n_patches, d.hidden), 1.0, train=True,
                                                     **self._policy.next_dropout())
@@ -104,7 +112,7 @@ class SFTTrainer:
             eng.seq_logprobs_bwd(self.llm, sv2, torch.zeros_like(logp2), d_feats=d_feats2, d_ent=-d_ent)
             if vsv2 is not None:
                 self.vision.backward(vsv2, d_feats2.view(B * d.n_patches, d.hidden))
-        eng.seq_logprobs_bwd(self.llm, sv, -(mask.float() / n) * loss_scale, d_feats=d_feats, d_ent=d_ent)
+        eng.seq_logprobs_bwd(self.llm, sv, -(mask.float() / n) * loss_scale, d_feats=d_feats, d_ent=d_ent, layer_done=self.layer_done_hook)
         self.vision.backward(vsv, d_feats.view(B * d.n_patches, d.hidden))
         return float(loss)
 

@@ -131,22 +131,67 @@ class VisionTrainPath:
         self.proj0_t, self.proj2_t = base.proj0.t().contiguous(), base.proj2.t().contiguous()
 
     def _lora_linear(self, x, w, bias, a, b, out, t, *, groups=1, residual=None):
-        """out = x W^T + bias + s (x A^T) B^T (+ residual); t = s x A^T is kept for the wgrad."""
+        """out = x W^T + bias + s (x A^T) B^T (+ residual); t = s x A^T is kept for the wgrad.  out None: t only (the backward's recompute of a
+        product whose result no gradient reads)."""
         d = self.d
         L.gemm_nt(x, a, t, alpha=d.lora_scale)
+        if out is None:
+            return
         kw = dict(a2_group_n=w.shape[0] // groups, a2_group_stride=d.lora_r) if groups > 1 else {}
         L.gemm_nt(x, w, out, a2=t, b2=b, bias=bias, residual=residual, **kw)
 
-    @torch.no_grad()
-    def forward(self, pixels: torch.Tensor):
-        """pixels [B,3,S,S] -> (feats [B*P, H] bf16, saved)."""
-        d, b, ad = self.d, self.base, self.ad
+    def _layer_bufs(self, B):
+        """The activations of ONE CLIP layer that its backward reads besides the layer's input."""
+        d = self.d
+        vh, vf, r, T = d.v_hidden, d.v_ffn, d.lora_r, d.n_patches + 1
+        M = B * T
+        e = lambda *shape, dtype=BF: torch.empty(*shape, dtype=dtype, device=self.dev)
+        return dict(n1=e(M, vh), qkv=e(M, 3 * vh), t_qkv=e(M, 3 * r), att=e(M, vh), lse=e(B, d.v_heads, T, dtype=torch.float32),
+                    t_o=e(M, r), x2=e(M, vh), n2=e(M, vh), t_1=e(M, r), z1=e(M, vf), f1=e(M, vf), t_2=e(M, r))
+
+    def _layer_fwd(self, j, x, s, out, B):
+        """CLIP layer j from its input x [B*T, vh] into the activation set s (`_layer_bufs`) and its output `out`.  The ONE layer body: `forward`
+        runs it per layer, the checkpointed `backward` re-runs it with out = None (fc2's result is the next layer's input, which is saved)."""
+        d, ad, w = self.d, self.ad, self.base.vlayers[j]
         st = L.stream()
-        B = pixels.shape[0]
-        P, vh, vf, r, H = d.n_patches, d.v_hidden, d.v_ffn, d.lora_r, d.hidden
-        T = P + 1
+        vh, vf, T = d.v_hidden, d.v_ffn, d.n_patches + 1
         M = B * T
         hd = vh // d.v_heads
+        L.call("opadpo_layernorm_fwd", L.ptr(x), L.ptr(w["layer_norm1_w"]), L.ptr(w["layer_norm1_b"]), L.ptr(s["n1"]), M, vh, d.v_eps, st)
+        self._lora_linear(s["n1"], w["wqkv"], w["bqkv"], ad.w(j, "a_qkv"), ad.w(j, "b_qkv"), s["qkv"], s["t_qkv"], groups=3)
+        qkv = s["qkv"]
+        L.call("opadpo_attn_fwd", L.ptr(qkv), qkv.data_ptr() + 2 * vh, qkv.data_ptr() + 4 * vh, 3 * vh, L.ptr(s["att"]), vh,
+               L.ptr(s["lse"]), None, B, T, d.v_heads, hd, 0, hd ** -0.5, 0, 0, st)
+        self._lora_linear(s["att"], w["wo"], w["bo"], ad.w(j, "a_o"), ad.w(j, "b_o"), s["x2"], s["t_o"], residual=x)
+        L.call("opadpo_layernorm_fwd", L.ptr(s["x2"]), L.ptr(w["layer_norm2_w"]), L.ptr(w["layer_norm2_b"]), L.ptr(s["n2"]), M, vh, d.v_eps, st)
+        self._lora_linear(s["n2"], w["fc1"], w["b1"], ad.w(j, "a_f1"), ad.w(j, "b_f1"), s["z1"], s["t_1"])
+        L.call("opadpo_act_fwd", L.ptr(s["z1"]), L.ptr(s["f1"]), M * vf, L.ACT_QUICK_GELU, st)
+        self._lora_linear(s["f1"], w["fc2"], w["b2"], ad.w(j, "a_f2"), ad.w(j, "b_f2"), out, s["t_2"], residual=s["x2"])
+
+    def _proj_bufs(self, B):
+        d = self.d
+        n, r, H = B * d.n_patches, d.lora_r, d.hidden
+        e = lambda *shape: torch.empty(*shape, dtype=BF, device=self.dev)
+        return dict(t_p0=e(n, r), zp=e(n, H), h0=e(n, H), t_p2=e(n, r))
+
+    def _proj_fwd(self, tok, sp, feats):
+        """mm_projector (mlp2x_gelu) from its input tok [B*P, vh] into the activation set sp (`_proj_bufs`) and `feats` (None in the recompute)."""
+        d, b, ad, pj = self.d, self.base, self.ad, self.d.v_used_layers
+        self._lora_linear(tok, b.proj0, b.proj0_b, ad.w(pj, "a_p0"), ad.w(pj, "b_p0"), sp["zp"], sp["t_p0"])
+        L.call("opadpo_act_fwd", L.ptr(sp["zp"]), L.ptr(sp["h0"]), tok.shape[0] * d.hidden, L.ACT_GELU, L.stream())
+        self._lora_linear(sp["h0"], b.proj2, b.proj2_b, ad.w(pj, "a_p2"), ad.w(pj, "b_p2"), feats, sp["t_p2"])
+
+    @torch.no_grad()
+    def forward(self, pixels: torch.Tensor, checkpoint: bool = False):
+        """pixels [B,3,S,S] -> (feats [B*P, H] bf16, saved).  checkpoint: `saved` keeps each layer's INPUT and the projector's input only (the
+        layers run through one reused activation set); `backward` re-runs a layer from its input before it walks it.  Same features, same
+        gradients, bit for bit: every kernel here is deterministic and the recompute is `_layer_fwd` / `_proj_fwd` again."""
+        d, b = self.d, self.base
+        st = L.stream()
+        B = pixels.shape[0]
+        P, vh, H = d.n_patches, d.v_hidden, d.hidden
+        T = P + 1
+        M = B * T
         e = lambda *shape, dtype=BF: torch.empty(*shape, dtype=dtype, device=self.dev)
         px = pixels.to(device=self.dev, dtype=BF).contiguous()
         cols = e(B * P, d.patch_kpad)
@@ -157,33 +202,23 @@ class VisionTrainPath:
         L.call("opadpo_vision_embed", L.ptr(patches), L.ptr(b.cls), L.ptr(b.pos), L.ptr(x0), B, P, vh, st)
         x = e(M, vh)
         L.call("opadpo_layernorm_fwd", L.ptr(x0), L.ptr(b.pre_ln_w), L.ptr(b.pre_ln_b), L.ptr(x), M, vh, d.v_eps, st)
-        sv = {"B": B, "layers": []}
-        for j, w in enumerate(b.vlayers):
-            s = dict(x=x, n1=e(M, vh), qkv=e(M, 3 * vh), t_qkv=e(M, 3 * r), att=e(M, vh), lse=e(B, d.v_heads, T, dtype=torch.float32),
-                     t_o=e(M, r), x2=e(M, vh), n2=e(M, vh), t_1=e(M, r), z1=e(M, vf), f1=e(M, vf), t_2=e(M, r))
-            L.call("opadpo_layernorm_fwd", L.ptr(x), L.ptr(w["layer_norm1_w"]), L.ptr(w["layer_norm1_b"]), L.ptr(s["n1"]), M, vh, d.v_eps, st)
-            self._lora_linear(s["n1"], w["wqkv"], w["bqkv"], ad.w(j, "a_qkv"), ad.w(j, "b_qkv"), s["qkv"], s["t_qkv"], groups=3)
-            qkv = s["qkv"]
-            L.call("opadpo_attn_fwd", L.ptr(qkv), qkv.data_ptr() + 2 * vh, qkv.data_ptr() + 4 * vh, 3 * vh, L.ptr(s["att"]), vh,
-                   L.ptr(s["lse"]), None, B, T, d.v_heads, hd, 0, hd ** -0.5, 0, 0, st)
-            self._lora_linear(s["att"], w["wo"], w["bo"], ad.w(j, "a_o"), ad.w(j, "b_o"), s["x2"], s["t_o"], residual=x)
-            L.call("opadpo_layernorm_fwd", L.ptr(s["x2"]), L.ptr(w["layer_norm2_w"]), L.ptr(w["layer_norm2_b"]), L.ptr(s["n2"]), M, vh, d.v_eps, st)
-            self._lora_linear(s["n2"], w["fc1"], w["b1"], ad.w(j, "a_f1"), ad.w(j, "b_f1"), s["z1"], s["t_1"])
-            L.call("opadpo_act_fwd", L.ptr(s["z1"]), L.ptr(s["f1"]), M * vf, L.ACT_QUICK_GELU, st)
-            x = e(M, vh)
-            self._lora_linear(s["f1"], w["fc2"], w["b2"], ad.w(j, "a_f2"), ad.w(j, "b_f2"), x, s["t_2"], residual=s["x2"])
-            sv["layers"].append(s)
+        # the patch embedding and the pre-layernorm are frozen and the backward stops at the first block's input: nothing of them is kept
+        sv = {"B": B, "checkpoint": bool(checkpoint), "layers": []}
+        scratch = self._layer_bufs(B) if checkpoint else None
+        for j in range(len(b.vlayers)):
+            s = scratch if checkpoint else self._layer_bufs(B)
+            out = e(M, vh)
+            self._layer_fwd(j, x, s, out, B)
+            sv["layers"].append(dict(x=x) if checkpoint else dict(s, x=x))
+            x = out
         idx = (torch.arange(B, device=self.dev, dtype=torch.int32)[:, None] * T
                + torch.arange(1, T, device=self.dev, dtype=torch.int32)[None, :]).reshape(-1).contiguous()
         tok = e(B * P, vh)
         L.call("opadpo_gather_rows", L.ptr(x), vh, L.ptr(idx), L.ptr(tok), B * P, vh, st)
-        pj = self.d.v_used_layers
-        sp = dict(idx=idx, tok=tok, t_p0=e(B * P, r), zp=e(B * P, H), h0=e(B * P, H), t_p2=e(B * P, r))
-        self._lora_linear(tok, b.proj0, b.proj0_b, ad.w(pj, "a_p0"), ad.w(pj, "b_p0"), sp["zp"], sp["t_p0"])
-        L.call("opadpo_act_fwd", L.ptr(sp["zp"]), L.ptr(sp["h0"]), B * P * H, L.ACT_GELU, st)
+        sp = self._proj_bufs(B)
         feats = e(B * P, H)
-        self._lora_linear(sp["h0"], b.proj2, b.proj2_b, ad.w(pj, "a_p2"), ad.w(pj, "b_p2"), feats, sp["t_p2"])
-        sv["proj"] = sp
+        self._proj_fwd(tok, sp, feats)
+        sv["proj"] = dict(idx=idx, tok=tok) if checkpoint else dict(sp, idx=idx, tok=tok)
         return feats, sv
 
     def _lora_linear_bwd(self, dY, x, t, w_t, layer, a_name, b_name, dx, *, groups=1):
@@ -216,7 +251,11 @@ class VisionTrainPath:
         hd = vh // d.v_heads
         e = lambda *shape, dtype=BF: torch.empty(*shape, dtype=dtype, device=self.dev)
         dF = d_feats.to(device=self.dev, dtype=BF).contiguous()
+        ck = sv.get("checkpoint", False)
         sp, pj = sv["proj"], d.v_used_layers
+        if ck:                                   # the projector again from its saved input (feats themselves are not needed)
+            sp = dict(self._proj_bufs(B), idx=sp["idx"], tok=sp["tok"])
+            self._proj_fwd(sp["tok"], sp, None)
         d_h0 = e(B * P, H)
         self._lora_linear_bwd(dF, sp["h0"], sp["t_p2"], self.proj2_t, pj, "a_p2", "b_p2", d_h0)
         d_zp = e(B * P, H)
@@ -225,8 +264,13 @@ class VisionTrainPath:
         self._lora_linear_bwd(d_zp, sp["tok"], sp["t_p0"], self.proj0_t, pj, "a_p0", "b_p0", d_tok)
         dx = torch.zeros(M, vh, dtype=BF, device=self.dev)                    # CLS rows get no gradient from the projector
         L.call("opadpo_scatter_rows", L.ptr(d_tok), L.ptr(sp["idx"]), L.ptr(dx), vh, B * P, vh, st)
+        sp = None
+        scratch = self._layer_bufs(B) if ck else None       # ONE layer-sized set: every layer is re-run into it right before its backward
         for j in range(len(sv["layers"]) - 1, -1, -1):
             s, w, wt = sv["layers"][j], b.vlayers[j], self.wt[j]
+            if ck:
+                self._layer_fwd(j, s["x"], scratch, None, B)
+                s = dict(scratch, x=s["x"])
             d_f1 = e(M, vf)
             self._lora_linear_bwd(dx, s["f1"], s["t_2"], wt["fc2"], j, "a_f2", "b_f2", d_f1)
             d_z1 = e(M, vf)

@@ -8,7 +8,13 @@ largest pair count whose PREDICTED footprint stays under --hbm-fraction of the d
 prediction = what does not scale with the batch (allocated before the first step) + the measured on-mode peak above it, scaled by pairs / --pairs;
 the activation arena, the workspaces and the batch all grow linearly in the pairs, and the head only gets cheaper once it goes chunked.
 The trial is also capped by --max-pairs (row counts the kernels have been run at); the memory-bound count is reported next to it.
-Prints one JSON line."""
+Prints one JSON line.
+
+--stage opa: the OPA LoRA-SFT stage instead (run/train_opa.sh: per-device batch 4, query 128 + response 896, LoRA on LLM + CLIP tower + projector).  Per
+micro-batch (SFTTrainer.loss_and_backward, gradients zeroed after it) with the entropy regulariser off and on (its masked pixels are made once, outside
+the timed region): median ms of alternating off / on blocks, the allocator's peak per mode and the context's own `bytes_peak` (one context per mode:
+the figure is a lifetime maximum).  On a tree whose SFTTrainer has no `gradient_checkpointing` keyword only the off blocks run: the same command
+there gives the parent's figure for the off-against-parent comparison."""
 import argparse
 import json
 import os
@@ -29,8 +35,77 @@ from opadpo_amd.policy import AutoregressivePolicy  # noqa: E402
 from opadpo_amd.synth import init_lora, init_weights, synth_pairs  # noqa: E402
 
 
+def main_opa(a):
+    import inspect
+    from opadpo_amd.sft import SFTTrainer
+    from opadpo_amd.vision_train import VisionLoraAdapter
+    L.load()
+    dev = torch.device("cuda:0")
+    d = LlavaDims.llava15_7b() if a.model == "7b" else LlavaDims.tiny()
+    q_len, t_len = (128, 896) if a.model == "7b" else (16, 16)
+    has_switch = "gradient_checkpointing" in inspect.signature(SFTTrainer.__init__).parameters
+    modes = (False, True) if has_switch else (False,)
+    base = BaseWeights(d, init_weights(d, seed=0, device=dev), dev, need_backward=True)
+    lora = init_lora(d, seed=1, device=dev, with_vision=True)
+    llm, vis = LoraAdapter(d, lora, dev, trainable=True), VisionLoraAdapter(d, lora, dev)
+    tr = {on: SFTTrainer(CtxEngine(base), llm, vis, response_len=t_len, lr=1e-6, entropy_mask_ratio=0.8, entropy_loss_coef=0.01,
+                         **(dict(gradient_checkpointing=on) if has_switch else {})) for on in modes}
+    pool = []
+    for i in range(a.steps):
+        p = synth_pairs(d, a.batch, q_len, t_len, seed=i, device=dev)
+        g = torch.Generator().manual_seed(1000 + i)
+        keep = (torch.rand(a.batch, 1, d.image_size // d.patch, d.image_size // d.patch, generator=g) > 0.8).to(dev)
+        masked = p["images"] * keep.repeat_interleave(d.patch, 2).repeat_interleave(d.patch, 3)
+        pool.append(dict(images=p["images"], queries=p["queries"], queries_attn_masks=p["queries_attn_masks"], responses=p["chosen"], masked_images=masked))
+    torch.cuda.synchronize()
+    fixed = torch.cuda.memory_allocated()
+
+    def block(on, entropy):
+        t = tr[on]
+        t.entropy_loss = entropy
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        t0 = time.perf_counter()
+        for b in pool:
+            t.loss_and_backward(b["images"], b["queries"], b["queries_attn_masks"], b["responses"], masked_images=b["masked_images"] if entropy else None)
+            llm.grad.zero_()
+            vis.grad.zero_()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / len(pool) * 1e3, torch.cuda.max_memory_allocated()
+
+    out = {"metric": "OPA LoRA-SFT micro-batch (loss_and_backward) with gradient checkpointing vs without, same process, alternating blocks", "stage": "opa",
+           "model": a.model, "batch": a.batch, "query_len": q_len, "response_len": t_len, "modes": ["off", "on"] if has_switch else ["off"],
+           "fixed_allocated_GB": fixed / 1e9}
+    name = {False: "off", True: "on"}
+    for entropy in (False, True):
+        for on in modes:
+            block(on, entropy)                                  # warm-up of each form (allocator, workspaces)
+        t, peak = {on: [] for on in modes}, {on: 0 for on in modes}
+        for _ in range(a.blocks):
+            for on in modes:
+                ms, pk = block(on, entropy)
+                t[on].append(ms)
+                peak[on] = max(peak[on], pk)
+        med = {on: sorted(v)[len(v) // 2] for on, v in t.items()}
+        leg = {"ms_" + name[on]: med[on] for on in modes}
+        leg.update({"blocks_" + name[on] + "_ms": t[on] for on in modes})
+        leg["hbm_peak_allocated_GB"] = {name[on]: peak[on] / 1e9 for on in modes}
+        if has_switch:
+            leg.update(extra_ms=med[True] - med[False], extra_fraction=med[True] / med[False] - 1.0, spread_ms_off=max(t[False]) - min(t[False]),
+                       peak_on_below_off=bool(peak[True] < peak[False]))
+        out["entropy_loss_" + ("on" if entropy else "off")] = leg
+    # lifetime maximum of each context: the entropy-on micro-batch (two training forwards alive) sets it
+    out["ctx_bytes_peak_GB"] = {name[on]: int(tr[on].engine._lib.opadpo_ctx_bytes_peak(tr[on].engine.ctx)) / 1e9 for on in modes}
+    print(json.dumps(out), flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--stage", default="dpo", choices=["dpo", "opa"], help="dpo: the trainer step of the benchmark shape; opa: the LoRA-SFT micro-batch")
+    ap.add_argument("--batch", type=int, default=4, help="--stage opa: per-device micro-batch")
     ap.add_argument("--model", default="7b", choices=["7b", "tiny"])
     ap.add_argument("--pairs", type=int, default=22)
     ap.add_argument("--blocks", type=int, default=3)
@@ -40,6 +115,8 @@ def main():
                     "padded gate|up activation of 7B ([rows, 2 x 11008] bf16) passes 2^31 bytes, a size no test of the kernels has run at")
     ap.add_argument("--json", default=None, help="also write the result to this file")
     a = ap.parse_args()
+    if a.stage == "opa":
+        return main_opa(a)
     L.load()
     dev = torch.device("cuda:0")
     d = LlavaDims.llava15_7b() if a.model == "7b" else LlavaDims.tiny()
