@@ -191,6 +191,31 @@ __global__ void gather_cells_kernel(const float* a, const float* b, const int32_
 
 inline dim3 g1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
+// bump carving of one arena (base == nullptr: sizes only)
+struct Carve {
+  char* base; size_t off = 0;
+  explicit Carve(void* p) : base((char*)p) {}
+  template <typename T> T* take(size_t n) { T* r = base ? (T*)(base + off) : nullptr; off += up(n * sizeof(T)); return r; }
+};
+
+// what one Llama decoder layer writes besides the residual stream: the activations its backward reads
+struct LayerBufs { bf16_t *n1, *qkv, *t_qkv, *attn, *t_o, *n2, *t_gu, *gu, *act, *t_d; float *rstd1, *rstd2, *lse, *h; };
+// `nb` layer slots of M rows (S sequences of at most L positions), every buffer [nb][...]: the returned LayerBufs is slot 0.  The activation arena
+// (saved_layout) and the rollout prefill's scratch carve their per-layer part here - order and sizes are what opadpo_ctx_bytes_peak and the arena hints
+// are made of
+LayerBufs carve_layer_bufs(Carve& cv, const opadpo_dims& d, size_t nb, size_t M, size_t S, size_t L) {
+  const size_t H = d.hidden, F = d.ffn, r = d.lora_r;
+  LayerBufs b;
+  b.n1 = cv.take<bf16_t>(nb * M * H); b.rstd1 = cv.take<float>(nb * M);
+  b.qkv = cv.take<bf16_t>(nb * M * 3 * H); b.t_qkv = cv.take<bf16_t>(nb * M * 3 * r);
+  b.attn = cv.take<bf16_t>(nb * M * H); b.lse = cv.take<float>(nb * S * d.n_heads * L);
+  b.t_o = cv.take<bf16_t>(nb * M * r); b.h = cv.take<float>(nb * M * H);
+  b.n2 = cv.take<bf16_t>(nb * M * H); b.rstd2 = cv.take<float>(nb * M);
+  b.t_gu = cv.take<bf16_t>(nb * M * 2 * r); b.gu = cv.take<bf16_t>(nb * M * 2 * F);
+  b.act = cv.take<bf16_t>(nb * M * F); b.t_d = cv.take<bf16_t>(nb * M * r);
+  return b;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -203,8 +228,7 @@ struct opadpo_saved {
   int ckpt = 0;                     // gradient checkpointing (opadpo_ctx_set_grad_checkpoint; training passes only): ONE slot, the backward re-runs a layer's
                                     // forward from the kept x_i into it before that layer's backward
   float* x = nullptr;               // [(nl+1) or 2][M,H] fp32 residual stream
-  bf16_t *n1, *qkv, *t_qkv, *attn, *t_o, *n2, *t_gu, *gu, *act, *t_d;
-  float *rstd1, *rstd2, *lse, *h;
+  LayerBufs lb;                     // slot 0 of the nb per-layer slots (slot())
   uint8_t* key_mask; float* hs; bf16_t* hn; float* rstd_f; float* logits; float* lse_head; float* ent;
   int32_t *rows, *labels;
   int Rc = 0;                       // head rows actually computed: R (padded layout) or the number of valid response cells (ragged)
@@ -275,8 +299,9 @@ struct opadpo_ctx {
   struct Decode {
     bool active = false; void* arena = nullptr; size_t bytes = 0;
     int B = 0, Lp = 0, max_ctx = 0, adapter = 0, max_new = 0;
-    bf16_t *kc, *vc; uint8_t* key_mask; float *x, *x2, *hs; bf16_t *hn, *n1, *qkv, *t_qkv, *att, *t_o, *n2, *t_gu, *gu, *act, *t_d, *emb;
-    float *hb, *rstd, *logits; int32_t *cur_tok, *step_d, *pos_d; uint8_t* finished; void* ws; size_t ws_bytes;
+    bf16_t *kc, *vc; uint8_t* key_mask; float *x, *x2, *hs; bf16_t *hn, *emb;
+    LayerBufs b;                    // the one layer slot of a step's B rows: h = post-attention residual stream, rstd1 = rstd2 = rstd, no lse
+    float *rstd, *logits; int32_t *cur_tok, *step_d, *pos_d; uint8_t* finished; void* ws; size_t ws_bytes;
     float *part_o, *part_d; int split_o = 1, split_d = 1; bool use64 = false;      // K-split partial tiles of the 9..64-token decode GEMMs
     int32_t* history; float temperature; int top_k; float top_p; uint64_t seed; int eos_id, pad_id, suppress_eos;
     // logit bias of every step and the step-0 scores (opadpo_ctx_set_logit_processors): `logit` = the host copy this generation took, the device tables
@@ -351,13 +376,6 @@ void* ws_grow(opadpo_ctx* c, void*& p, size_t& held, size_t bytes, hipStream_t s
 }
 void* ctx_ws(opadpo_ctx* c, size_t bytes, hipStream_t st) { return ws_grow(c, c->ws, c->ws_bytes, bytes, st); }
 
-// bump carving of one arena
-struct Carve {
-  char* base; size_t off = 0;
-  explicit Carve(void* p) : base((char*)p) {}
-  template <typename T> T* take(size_t n) { T* r = base ? (T*)(base + off) : nullptr; off += up(n * sizeof(T)); return r; }
-};
-
 // the kernel flags of a launch of this context
 KernelFlags ctx_flags(const opadpo_ctx* c) { return resolve_flags(process_flags(), c->kernel); }
 
@@ -412,8 +430,6 @@ LoraOff lora_off(const opadpo_dims& d) {
   return o;
 }
 
-inline bool lw_kind1(const opadpo_ctx::Adapter& ad) { return ad.kind == 1; }
-
 hipError_t ensure_rope(opadpo_ctx* c, int len, hipStream_t st) {
   if (c->cosb && c->rope_len >= len) return hipSuccess;
   if (c->cosb && !c->rope_own) return hipErrorInvalidValue;      // caller-provided tables are too short
@@ -442,10 +458,39 @@ hipError_t ensure_rope(opadpo_ctx* c, int len, hipStream_t st) {
 }
 
 // ---- one Llama decoder layer over M = S*Lp rows (model.py layer_fwd / mlp_fwd) ------------------------------------------------
-struct LayerBufs { bf16_t *n1, *qkv, *t_qkv, *attn, *t_o, *n2, *t_gu, *gu, *act, *t_d; float *rstd1, *rstd2, *lse, *h; };
 // LoRA dropout of a training forward (nullptr = off: the launches below are the ones without it): every A product reads masked copies of its input
 // from xm instead of the input - q|k|v and gate|up one copy per module side by side, selected per r-wide column group (grouped A1)
 struct DropFwd { LoraDropout dp; bf16_t* xm; };
+
+#define TRY(expr)                          \
+  do {                                     \
+    hipError_t e_ = (expr);                \
+    if (e_ != hipSuccess) return e_;       \
+  } while (0)
+
+// ---- the "LoRA Linear" forward: t = s . x~ . A^T, then y = x . W^T + t . B^T as the K-tail of the base product.  `g` is the base product x . W^T as the call
+// site decorated it (fused RoPE, fp32 residual, OPADPO_ACT_SWIGLU_PAIR, OPADPO_GEMM_STREAM - the hint is passed on to the A product); its A1 / lda1 / K1 / M /
+// N describe the Linear.  The output columns are `groups` fused modules of N / groups columns (3: q|k|v, 2: gate|up, 1: o, down), each with its r-wide slice of
+// t.  lw == nullptr (no adapter, or a merged one): the base product alone.
+// dr (LoRA dropout of a training forward, nullptr = off): the A product reads masked copies x~ of the input from dr->xm - one per module, side by side, selected
+// per r-wide column group (grouped A1); modules module0 .. module0 + groups - 1, rows hashed with drop_rows (nullptr: their index).
+// a_only: stop after the A product (the down projection of a recomputed layer).
+struct LoraLin { const bf16_t* lw; size_t a, b; int groups; bf16_t* t; int module0; const int32_t* drop_rows; };
+hipError_t lora_linear_fwd(opadpo_ctx* c, int layer, GemmNTArgs g, const LoraLin& l, const DropFwd* dr, hipStream_t st, bool a_only = false) {
+  if (l.lw) {
+    const int r = c->d.lora_r, n = l.groups, K = g.K1;
+    GemmNTArgs ga = gemm(g.A1, g.lda1, l.lw + l.a, K, K, l.t, n * r, 0, g.M, n * r);
+    ga.alpha = c->d.lora_alpha / c->d.lora_r; ga.act |= g.act & OPADPO_GEMM_STREAM;
+    if (dr) {
+      TRY(launch_lora_dropout_fwd(g.A1, dr->xm, g.M, K, n, dr->dp, layer, l.module0, l.drop_rows, st));
+      ga.A1 = dr->xm;
+      if (n > 1) { ga.lda1 = n * K; ga.a1_group_n = r; ga.a1_group_stride = K; }
+    }
+    TRY(run_gemm(c, ga, st));
+    tail(g, l.t, n * r, l.lw + l.b, r, r, n > 1 ? g.N / n : 0, n > 1 ? r : 0);
+  }
+  return a_only ? hipSuccess : run_gemm(c, g, st);
+}
 
 // ydef != nullptr ("deferred residual", the full-sequence passes): the down projection writes its fp32 product to ydef WITHOUT the
 // residual - the RMSNorm that follows adds it (rmsnorm_sum_fwd: x = h + y in the same fp32 arithmetic, so h / x keep their bits).
@@ -457,55 +502,40 @@ struct DropFwd { LoraDropout dp; bf16_t* xm; };
 hipError_t mlp_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const float* h, float* xo, const LayerBufs& b, int M, int stream_hint, hipStream_t st,
                    float* ydef = nullptr, bool norm_done = false, const DropFwd* dr = nullptr, const int32_t* drop_rows = nullptr, bool recompute = false) {
   const opadpo_dims& d = c->d;
-  const int H = d.hidden, F = d.ffn, r = d.lora_r;
-  const float s = d.lora_alpha / d.lora_r;
+  const int H = d.hidden, F = d.ffn;
   const opadpo_layer_weights& w0 = c->layers[i];
-  const bool merged = ad.kind == 2;
-  const opadpo_layer_weights& w = merged ? ad.merged[i] : w0;
+  const opadpo_layer_weights& w = ad.kind == 2 ? ad.merged[i] : w0;
   const LoraOff o = lora_off(d);
   const bf16_t* lw = ad.kind == 1 ? ad.work + (size_t)i * o.layer : nullptr;
-  hipError_t e;
-  if (!norm_done && (e = launch_rmsnorm_fwd(h, 1, w0.ln2, b.n2, b.rstd2, M, H, d.rms_eps, st)) != hipSuccess) return e;
-  bool have_gu = true;
-  if (lw) {
-    GemmNTArgs g1_ = gemm(b.n2, H, lw + o.a_gu, H, H, b.t_gu, 2 * r, 0, M, 2 * r); g1_.alpha = s; g1_.act |= stream_hint;
-    if (dr) {                                       // gate, up: modules 4, 5
-      if ((e = launch_lora_dropout_fwd(b.n2, dr->xm, M, H, 2, dr->dp, i, 4, drop_rows, st)) != hipSuccess) return e;
-      g1_.A1 = dr->xm; g1_.lda1 = 2 * H; g1_.a1_group_n = r; g1_.a1_group_stride = H;
-    }
-    if ((e = run_gemm(c, g1_, st)) != hipSuccess) return e;
-    GemmNTArgs g2 = gemm(b.n2, H, w.wgu, H, H, b.gu, 2 * F, 0, M, 2 * F); tail(g2, b.t_gu, 2 * r, lw + o.b_gu, r, r, F, r); g2.act |= stream_hint;
-    if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
-  } else if (merged && ad.swiglu_pair) {        // SwiGLU fused into the projection's epilogue (rows per 128 = [64 gate | 64 up])
-    GemmNTArgs g2 = gemm(b.n2, H, w.wgu, H, H, b.act, F, 0, M, 2 * F); g2.act = OPADPO_ACT_SWIGLU_PAIR | stream_hint;
-    if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
-    have_gu = false;
-  } else {
-    GemmNTArgs g2 = gemm(b.n2, H, w.wgu, H, H, b.gu, 2 * F, 0, M, 2 * F); g2.act |= stream_hint;
-    if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
-  }
-  if (have_gu && (e = launch_silu_mul_fwd(b.gu, b.act, M, F, st)) != hipSuccess) return e;
-  if (lw) {
-    GemmNTArgs g3 = gemm(b.act, F, lw + o.a_d, F, F, b.t_d, r, 0, M, r); g3.alpha = s; g3.act |= stream_hint;
-    if (dr) {                                       // down: module 6
-      if ((e = launch_lora_dropout_fwd(b.act, dr->xm, M, F, 1, dr->dp, i, 6, drop_rows, st)) != hipSuccess) return e;
-      g3.A1 = dr->xm;
-    }
-    if ((e = run_gemm(c, g3, st)) != hipSuccess) return e;
-    if (recompute) return hipSuccess;               // t_d is the last thing the backward reads: no down product, nothing written to xo / ydef
-    GemmNTArgs g4 = gemm(b.act, F, w.wd, F, F, ydef ? ydef : xo, H, 1, M, H); tail(g4, b.t_d, r, lw + o.b_d, r, r); g4.act |= stream_hint;
-    if (!ydef) resid(g4, h, H, 1);
-    return run_gemm(c, g4, st);
-  }
-  if (recompute) return hipSuccess;
-  GemmNTArgs g4 = gemm(b.act, F, w.wd, F, F, ydef ? ydef : xo, H, 1, M, H); g4.act |= stream_hint;
-  if (!ydef) resid(g4, h, H, 1);
-  return run_gemm(c, g4, st);
+  if (!norm_done) TRY(launch_rmsnorm_fwd(h, 1, w0.ln2, b.n2, b.rstd2, M, H, d.rms_eps, st));
+  // merged adapter with paired rows: SwiGLU fused into the projection's epilogue (rows per 128 = [64 gate | 64 up]), act written directly
+  const bool pair = ad.kind == 2 && ad.swiglu_pair;
+  GemmNTArgs gu = pair ? gemm(b.n2, H, w.wgu, H, H, b.act, F, 0, M, 2 * F) : gemm(b.n2, H, w.wgu, H, H, b.gu, 2 * F, 0, M, 2 * F);
+  gu.act = (pair ? OPADPO_ACT_SWIGLU_PAIR : 0) | stream_hint;
+  TRY(lora_linear_fwd(c, i, gu, {lw, o.a_gu, o.b_gu, 2, b.t_gu, 4, drop_rows}, dr, st));      // gate, up: modules 4, 5
+  if (!pair) TRY(launch_silu_mul_fwd(b.gu, b.act, M, F, st));
+  GemmNTArgs dn = gemm(b.act, F, w.wd, F, F, ydef ? ydef : xo, H, 1, M, H); dn.act |= stream_hint;
+  if (!ydef) resid(dn, h, H, 1);
+  // recompute: t_d is the last thing the backward reads - no down product, nothing written to xo / ydef
+  return lora_linear_fwd(c, i, dn, {lw, o.a_d, o.b_d, 1, b.t_d, 6, drop_rows}, dr, st, recompute);      // down: module 6
 }
 
 struct Rag { const int32_t* meta; int stride, n_seg, rows; const int32_t* row_pos; };      // ragged rows of a pass (nullptr = padded)
 // top decoder layer on the rows the head reads only (opadpo_saved::Uc): U list, gathered attention output (kept), gathered input (scratch)
 struct TopRows { const int32_t* urow; int n; bf16_t* attn_u; float* x_u; };
+
+// causal attention over the q|k|v projection output of a layer (forward fields; the backward adds its own)
+AttnArgs attn_args(const opadpo_dims& d, const LayerBufs& b, const uint8_t* key_mask, int S, int L, int seg0, int seg1, const Rag* rg) {
+  const int H = d.hidden;
+  AttnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q = b.qkv; a.k = b.qkv + H; a.v = b.qkv + 2 * H; a.o = b.attn; a.lse = b.lse; a.key_mask = key_mask;
+  a.S = S; a.L = L; a.nh = d.n_heads; a.hd = d.head_dim; a.ld = 3 * H; a.ldo = H; a.causal = 1 | OPADPO_ATTN_SKIP_MASKED_Q;
+  a.scale = 1.0f / sqrtf((float)d.head_dim);
+  a.seg_prefix = seg0; a.seg_len = seg1;
+  if (rg) { a.seq_meta = rg->meta; a.meta_stride = rg->stride; a.n_seg = rg->n_seg; a.rows_total = rg->rows; a.seg_prefix = 0; a.seg_len = 0; }
+  return a;
+}
 
 // Input of the layer: x = res (+ yin when yin != nullptr: the previous layer's down-projection product, residual deferred).  x is written
 // to `x` (may alias res when yin is null), the layer leaves h = x + attention branch in b.h and its own down-projection product in Y:
@@ -517,63 +547,39 @@ hipError_t layer_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const 
                      const uint8_t* key_mask, int seg0, int seg1, bf16_t* kc, bf16_t* vc, int max_ctx, hipStream_t st, const Rag* rg = nullptr,
                      const TopRows* top = nullptr, const DropFwd* dr = nullptr, bool recompute = false) {
   const opadpo_dims& d = c->d;
-  const int H = d.hidden, r = d.lora_r, nh = d.n_heads, hd = d.head_dim;
-  if (dr && !lw_kind1(ad)) dr = nullptr;            // dropout belongs to the LoRA branch
+  const int H = d.hidden, nh = d.n_heads, hd = d.head_dim;
   const int M = rg ? rg->rows : S * Lp;
-  const float s = d.lora_alpha / d.lora_r;
   const opadpo_layer_weights& w0 = c->layers[i];
   const opadpo_layer_weights& w = ad.kind == 2 ? ad.merged[i] : w0;
   const LoraOff o = lora_off(d);
   const bf16_t* lw = ad.kind == 1 ? ad.work + (size_t)i * o.layer : nullptr;
-  hipError_t e;
-  const size_t MH = (size_t)M * H;
-  if (yin) e = launch_rmsnorm_sum_fwd(res, 1, yin, 1, MH, w0.ln1, x, b.n1, b.rstd1, M, H, d.rms_eps, st);
-  else e = (res == x) ? launch_rmsnorm_fwd(x, 1, w0.ln1, b.n1, b.rstd1, M, H, d.rms_eps, st) : hipErrorInvalidValue;
-  if (e != hipSuccess) return e;
+  if (yin) TRY(launch_rmsnorm_sum_fwd(res, 1, yin, 1, (size_t)M * H, w0.ln1, x, b.n1, b.rstd1, M, H, d.rms_eps, st));
+  else TRY((res == x) ? launch_rmsnorm_fwd(x, 1, w0.ln1, b.n1, b.rstd1, M, H, d.rms_eps, st) : hipErrorInvalidValue);
   // rotary embedding: on ragged rows (per-row positions at hand) inside the q|k|v projection's epilogue, table-free - one 130-us pass over
   // q and k less per layer and pass; context flag bit 11 keeps the separate in-place kernel (also: padded rows, head_dim 64, small problems
   // that the 256x256 kernel does not take)
   const bool fuse_rope = rg && hd == 128 && (3 * H) % 256 == 0 && !c->rope_own_kernel &&
                          (double)M * H * 2 < 4.0e9 && ((M + 255) / 256) * (3 * H / 256) >= 150;
-  auto with_rope = [&](GemmNTArgs& g) { if (fuse_rope) { g.rope_pos = rg->row_pos; g.rope_l2theta = log2f(d.rope_theta); g.rope_cols = 2 * H; } };
-  if (lw) {
-    GemmNTArgs g1_ = gemm(b.n1, H, lw + o.a_qkv, H, H, b.t_qkv, 3 * r, 0, M, 3 * r); g1_.alpha = s;
-    if (dr) {                                       // q, k, v: modules 0..2, three masks over the same n1
-      if ((e = launch_lora_dropout_fwd(b.n1, dr->xm, M, H, 3, dr->dp, i, 0, nullptr, st)) != hipSuccess) return e;
-      g1_.A1 = dr->xm; g1_.lda1 = 3 * H; g1_.a1_group_n = r; g1_.a1_group_stride = H;
-    }
-    if ((e = run_gemm(c, g1_, st)) != hipSuccess) return e;
-    GemmNTArgs g2 = gemm(b.n1, H, w.wqkv, H, H, b.qkv, 3 * H, 0, M, 3 * H); tail(g2, b.t_qkv, 3 * r, lw + o.b_qkv, r, r, H, r);
-    with_rope(g2);
-    if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
-  } else {
-    GemmNTArgs g2 = gemm(b.n1, H, w.wqkv, H, H, b.qkv, 3 * H, 0, M, 3 * H);
-    with_rope(g2);
-    if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
-  }
+  GemmNTArgs gq = gemm(b.n1, H, w.wqkv, H, H, b.qkv, 3 * H, 0, M, 3 * H);
+  if (fuse_rope) { gq.rope_pos = rg->row_pos; gq.rope_l2theta = log2f(d.rope_theta); gq.rope_cols = 2 * H; }
+  TRY(lora_linear_fwd(c, i, gq, {lw, o.a_qkv, o.b_qkv, 3, b.t_qkv, 0, nullptr}, dr, st));      // q, k, v: modules 0..2, three masks over the same n1
   // ragged passes that are too small (or too odd) for the fused epilogue rotate with the SAME table-free angles and arithmetic: the bits of a
   // row's q / k do not depend on the size of the batch around it, and the backward (always table-free on ragged rows) is the exact transpose
-  if (!fuse_rope && (e = launch_rope(b.qkv, 3 * H, c->cosb, c->sinb, M, Lp, 2 * nh, hd, 0, nullptr, seg0, seg1, st, rg ? rg->row_pos : nullptr,
-                                     rg ? log2f(d.rope_theta) : 0.f)) != hipSuccess) return e;
+  if (!fuse_rope) TRY(launch_rope(b.qkv, 3 * H, c->cosb, c->sinb, M, Lp, 2 * nh, hd, 0, nullptr, seg0, seg1, st, rg ? rg->row_pos : nullptr,
+                                  rg ? log2f(d.rope_theta) : 0.f));
   if (kc) {                                        // rollout prefill: post-RoPE k, v -> head-major KV cache
     hipLaunchKernelGGL(kv_fill_kernel, dim3(std::min<size_t>(4096, ((size_t)M * nh * (hd / 8) + 255) / 256)), dim3(256), 0, st, b.qkv, kc, vc, S, Lp, nh, hd, max_ctx);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    TRY(hipGetLastError());
   }
-  AttnArgs a;
-  memset(&a, 0, sizeof(a));
-  a.q = b.qkv; a.k = b.qkv + H; a.v = b.qkv + 2 * H; a.o = b.attn; a.lse = b.lse; a.key_mask = key_mask;
-  a.S = S; a.L = Lp; a.nh = nh; a.hd = hd; a.ld = 3 * H; a.ldo = H; a.causal = 1 | OPADPO_ATTN_SKIP_MASKED_Q; a.scale = 1.0f / sqrtf((float)hd);
-  a.seg_prefix = seg0; a.seg_len = seg1;
-  if (rg) { a.seq_meta = rg->meta; a.meta_stride = rg->stride; a.n_seg = rg->n_seg; a.rows_total = rg->rows; a.seg_prefix = 0; a.seg_len = 0; }
-  if ((e = launch_attn_fwd(a, ctx_flags(c), st)) != hipSuccess) return e;
+  TRY(launch_attn_fwd(attn_args(d, b, key_mask, S, Lp, seg0, seg1, rg), ctx_flags(c), st));
   // top layer with `top`: from here on only the rows the head reads exist (attention needed every row's k, v; nothing reads the
   // o-projection / MLP output of the other rows).  b.t_o / b.h / b.n2 / ... and Y then hold top->n COMPACT rows.
   int Mo = M;
   const bf16_t* attn = b.attn;
   const float* xr = x;
   if (top) {
-    if ((e = launch_gather_rows(b.attn, H, top->urow, top->attn_u, top->n, H, st)) != hipSuccess) return e;
-    if ((e = launch_gather_rows((const bf16_t*)x, 2 * H, top->urow, (bf16_t*)top->x_u, top->n, 2 * H, st)) != hipSuccess) return e;      // fp32 rows = 2H bf16 units
+    TRY(launch_gather_rows(b.attn, H, top->urow, top->attn_u, top->n, H, st));
+    TRY(launch_gather_rows((const bf16_t*)x, 2 * H, top->urow, (bf16_t*)top->x_u, top->n, 2 * H, st));      // fp32 rows = 2H bf16 units
     Mo = top->n; attn = top->attn_u; xr = top->x_u;
   }
   // fused residual (round 5, default; context flag bit 13 keeps the deferred form): h = x + attn . Wo leaves the o projection's DIRECT epilogue
@@ -582,47 +588,23 @@ hipError_t layer_fwd(opadpo_ctx* c, int i, const opadpo_ctx::Adapter& ad, const 
   // operands as rmsnorm_sum_fwd's: h / x keep their bits; the norm passes read 6 instead of 14 bytes per element.
   const bool fr = !c->resid_deferred;
   float* const o_dst = fr ? b.h : Y;
-  if (lw) {
-    GemmNTArgs g3 = gemm(attn, H, lw + o.a_o, H, H, b.t_o, r, 0, Mo, r); g3.alpha = s;
-    if (dr) {                                       // o: module 3; compact top layer: the rows hash with their row of the pass (urow), not their index in U
-      if ((e = launch_lora_dropout_fwd(attn, dr->xm, Mo, H, 1, dr->dp, i, 3, top ? top->urow : nullptr, st)) != hipSuccess) return e;
-      g3.A1 = dr->xm;
-    }
-    if ((e = run_gemm(c, g3, st)) != hipSuccess) return e;
-    GemmNTArgs g4 = gemm(attn, H, w.wo, H, H, o_dst, H, 1, Mo, H); tail(g4, b.t_o, r, lw + o.b_o, r, r);
-    if (fr) resid(g4, xr, H, 1);
-    if ((e = run_gemm(c, g4, st)) != hipSuccess) return e;
-  } else {
-    GemmNTArgs g4 = gemm(attn, H, w.wo, H, H, o_dst, H, 1, Mo, H);
-    if (fr) resid(g4, xr, H, 1);
-    if ((e = run_gemm(c, g4, st)) != hipSuccess) return e;
-  }
+  GemmNTArgs go = gemm(attn, H, w.wo, H, H, o_dst, H, 1, Mo, H);
+  if (fr) resid(go, xr, H, 1);
+  // o: module 3; compact top layer: the rows hash with their row of the pass (urow), not their index in U
+  TRY(lora_linear_fwd(c, i, go, {lw, o.a_o, o.b_o, 1, b.t_o, 3, top ? top->urow : nullptr}, dr, st));
   if (fr) {
-    if ((e = launch_rmsnorm_fwd(b.h, 1, w0.ln2, b.n2, b.rstd2, Mo, H, d.rms_eps, st)) != hipSuccess) return e;      // n2 = norm(h)
+    TRY(launch_rmsnorm_fwd(b.h, 1, w0.ln2, b.n2, b.rstd2, Mo, H, d.rms_eps, st));      // n2 = norm(h)
     return mlp_fwd(c, i, ad, b.h, Y, b, Mo, 0, st, nullptr, true, dr, top ? top->urow : nullptr, recompute);        // Y = h + down(..)
   }
-  if ((e = launch_rmsnorm_sum_fwd(xr, 1, Y, 1, (size_t)Mo * H, w0.ln2, b.h, b.n2, b.rstd2, Mo, H, d.rms_eps, st)) != hipSuccess) return e;      // h = x + attn . Wo, n2 = norm(h)
+  TRY(launch_rmsnorm_sum_fwd(xr, 1, Y, 1, (size_t)Mo * H, w0.ln2, b.h, b.n2, b.rstd2, Mo, H, d.rms_eps, st));      // h = x + attn . Wo, n2 = norm(h)
   return mlp_fwd(c, i, ad, b.h, nullptr, b, Mo, 0, st, Y, true, dr, top ? top->urow : nullptr, recompute);
 }
 
 size_t saved_layout(const opadpo_dims& d, opadpo_saved* sv, void* base) {
-  const size_t M = sv->M, H = d.hidden, F = d.ffn, r = d.lora_r, nl = d.n_layers, nb = sv->nb, R = sv->R;
+  const size_t M = sv->M, H = d.hidden, F = d.ffn, nl = d.n_layers, R = sv->R;
   Carve cv(base);
   sv->x = cv.take<float>((sv->train ? nl + 1 : 3) * M * H);      // x_0 .. x_{nl-1} (train) or two alternating slots, + ONE slot for the branch product Y
-  sv->n1 = cv.take<bf16_t>(nb * M * H);
-  sv->rstd1 = cv.take<float>(nb * M);
-  sv->qkv = cv.take<bf16_t>(nb * M * 3 * H);
-  sv->t_qkv = cv.take<bf16_t>(nb * M * 3 * r);
-  sv->attn = cv.take<bf16_t>(nb * M * H);
-  sv->lse = cv.take<float>(nb * (size_t)sv->S * d.n_heads * sv->L);
-  sv->t_o = cv.take<bf16_t>(nb * M * r);
-  sv->h = cv.take<float>(nb * M * H);
-  sv->n2 = cv.take<bf16_t>(nb * M * H);
-  sv->rstd2 = cv.take<float>(nb * M);
-  sv->t_gu = cv.take<bf16_t>(nb * M * 2 * r);
-  sv->gu = cv.take<bf16_t>(nb * M * 2 * F);
-  sv->act = cv.take<bf16_t>(nb * M * F);
-  sv->t_d = cv.take<bf16_t>(nb * M * r);
+  sv->lb = carve_layer_bufs(cv, d, sv->nb, M, sv->S, sv->L);
   sv->key_mask = cv.take<uint8_t>((size_t)sv->S * sv->L);
   sv->hs = cv.take<float>(R * H);
   sv->hn = cv.take<bf16_t>(R * H);
@@ -646,11 +628,11 @@ size_t saved_layout(const opadpo_dims& d, opadpo_saved* sv, void* base) {
 
 LayerBufs slot(const opadpo_dims& d, const opadpo_saved* sv, int k) {
   const size_t M = sv->M, H = d.hidden, F = d.ffn, r = d.lora_r;
-  LayerBufs b;
-  b.n1 = sv->n1 + k * M * H; b.rstd1 = sv->rstd1 + k * M; b.qkv = sv->qkv + k * M * 3 * H; b.t_qkv = sv->t_qkv + k * M * 3 * r;
-  b.attn = sv->attn + k * M * H; b.lse = sv->lse + (size_t)k * sv->S * d.n_heads * sv->L; b.t_o = sv->t_o + k * M * r;
-  b.h = sv->h + k * M * H; b.n2 = sv->n2 + k * M * H; b.rstd2 = sv->rstd2 + k * M; b.t_gu = sv->t_gu + k * M * 2 * r;
-  b.gu = sv->gu + k * M * 2 * F; b.act = sv->act + k * M * F; b.t_d = sv->t_d + k * M * r;
+  LayerBufs b = sv->lb;
+  b.n1 += k * M * H; b.rstd1 += k * M; b.qkv += k * M * 3 * H; b.t_qkv += k * M * 3 * r;
+  b.attn += k * M * H; b.lse += (size_t)k * sv->S * d.n_heads * sv->L; b.t_o += k * M * r;
+  b.h += k * M * H; b.n2 += k * M * H; b.rstd2 += k * M; b.t_gu += k * M * 2 * r;
+  b.gu += k * M * 2 * F; b.act += k * M * F; b.t_d += k * M * r;
   return b;
 }
 
@@ -1037,15 +1019,14 @@ int opadpo_seq_logprobs_fwd(opadpo_ctx* c, int adapter_id, const int32_t* ids, c
                   (sv->Uc > 0 && i == d.n_layers - 1) ? &top : nullptr, sv->drop_on ? &drop_fwd : nullptr));
     if (fr) { res = xo; yin = nullptr; } else { res = lb.h; yin = Y; }
   }
+  // final hidden state of the HEAD rows only (fp32 rows = 2H bf16 units): the last layer's output rows, or (deferred residual) x = h + y, the y rows
+  // parked in the logits buffer, which is written later
+  CKS(launch_gather_rows((const bf16_t*)res, 2 * H, sv->rows, (bf16_t*)sv->hs, R, 2 * H, st));
   if (fr) {
-    // final hidden state of the HEAD rows only: x = the last layer's output rows (fp32 rows = 2H bf16 units)
-    CKS(launch_gather_rows((const bf16_t*)res, 2 * H, sv->rows, (bf16_t*)sv->hs, R, 2 * H, st));
     CKS(launch_rmsnorm_fwd(sv->hs, 1, c->norm, sv->hn, sv->rstd_f, R, H, d.rms_eps, st));
   } else {
-  // final hidden state x = h + y of the HEAD rows only (fp32 rows = 2H bf16 units; the y rows park in the logits buffer, written later)
-  CKS(launch_gather_rows((const bf16_t*)res, 2 * H, sv->rows, (bf16_t*)sv->hs, R, 2 * H, st));
-  CKS(launch_gather_rows((const bf16_t*)Y, 2 * H, sv->rows, (bf16_t*)sv->logits, R, 2 * H, st));
-  CKS(launch_rmsnorm_sum_fwd(sv->hs, 1, sv->logits, 1, (size_t)R * H, c->norm, sv->hs, sv->hn, sv->rstd_f, R, H, d.rms_eps, st));
+    CKS(launch_gather_rows((const bf16_t*)Y, 2 * H, sv->rows, (bf16_t*)sv->logits, R, 2 * H, st));
+    CKS(launch_rmsnorm_sum_fwd(sv->hs, 1, sv->logits, 1, (size_t)R * H, c->norm, sv->hs, sv->hn, sv->rstd_f, R, H, d.rms_eps, st));
   }
   float* const head_logp = rg ? sv->logp_c : logp;
   if (sv->head_chunk > 0) {
@@ -1101,6 +1082,232 @@ int opadpo_saved_residual(opadpo_ctx* c, const opadpo_saved* sv, int layer, floa
 }
 
 // ---- LoRA backward (model.py seq_logprobs_bwd; rl_trainer.py:162 accelerator.backward) -----------------------------------------
+// workspace of a backward (c->ws; persists between the ranged calls of one backward)
+struct BwdWs {
+  bf16_t* dz; float* d_hn32; bf16_t* d_hn; float* d_hs;      // head: dz [R, vocab or chunk], d_hn32 = chunked head's fp32 accumulator
+  float* dX; bf16_t* dXb; float* d_h; bf16_t *d_hb, *d_n, *d_act, *d_gu, *d_attn, *dqkv; float* delta;
+  bf16_t *dt_r, *dt_2r, *dt_3r;
+  bf16_t* dt_ra;                    // dT of the o projection (dt_r keeps the down projection's until the grouped wgrad)
+  float* d_full;                    // compact top layer: its residual gradient scattered back to every row
+  float* tn_ws; size_t tn_ws_floats;      // partial tiles of the wgrads' ordered flush (1 float: the atomic flush, nothing to hold)
+  // LoRA dropout: the masked copies of the layer's four Linear inputs, regenerated from the saved activations ([down | gate, up | o | q, k, v]: they stay
+  // untouched until the grouped wgrad launch), and du = the un-fused dT . A products of one Linear
+  bf16_t *xm_d, *xm_gu, *xm_o, *xm_qkv, *du;
+  // checkpointed pass: scratch of the recomputed layers - the gathered input of the compact top layer (the forward borrowed sv->hs, which the head
+  // backward owns by now) and, deferred-residual form only, the o projection's product.  Never a kept x slot.
+  float *rc_xu, *rc_y;
+};
+size_t bwd_layout(const opadpo_ctx* c, const opadpo_saved* sv, size_t tn_ws_floats, BwdWs* w, void* base) {
+  const opadpo_dims& d = c->d;
+  const size_t M = sv->M, R = sv->Rc, H = d.hidden, F = d.ffn, r = d.lora_r, MH = M * H;
+  const size_t VC = sv->head_chunk;                   // chunked head: dz and the recomputed logits exist for one vocabulary chunk at a time
+  const bool drop = sv->drop_on != 0;
+  Carve cv(base);
+  w->dz = cv.take<bf16_t>(R * (VC > 0 ? VC : (size_t)d.vocab)); w->d_hn32 = cv.take<float>(VC > 0 ? R * H : 1);
+  w->d_hn = cv.take<bf16_t>(R * H); w->d_hs = cv.take<float>(R * H);
+  w->dX = cv.take<float>(MH); w->dXb = cv.take<bf16_t>(MH); w->d_h = cv.take<float>(MH); w->d_hb = cv.take<bf16_t>(MH);
+  w->d_n = cv.take<bf16_t>(MH); w->d_act = cv.take<bf16_t>(M * F); w->d_gu = cv.take<bf16_t>(M * 2 * F);
+  w->d_attn = cv.take<bf16_t>(MH); w->dqkv = cv.take<bf16_t>(M * 3 * H); w->delta = cv.take<float>((size_t)sv->S * d.n_heads * sv->L);
+  w->dt_r = cv.take<bf16_t>(M * r); w->dt_2r = cv.take<bf16_t>(M * 2 * r); w->dt_3r = cv.take<bf16_t>(M * 3 * r);
+  w->dt_ra = cv.take<bf16_t>(M * r);
+  w->d_full = cv.take<float>(sv->Uc > 0 ? MH : 1);
+  w->tn_ws = cv.take<float>(tn_ws_floats); w->tn_ws_floats = tn_ws_floats;
+  w->xm_d = cv.take<bf16_t>(drop ? M * (F + 6 * H) : 0);
+  if (base) { w->xm_gu = w->xm_d + M * F; w->xm_o = w->xm_gu + M * 2 * H; w->xm_qkv = w->xm_o + MH; }
+  w->du = cv.take<bf16_t>(drop ? M * std::max(3 * H, F) : 0);
+  w->rc_xu = cv.take<float>(sv->ckpt && sv->Uc > 0 ? (size_t)sv->Uc * H : 1);
+  w->rc_y = cv.take<float>(sv->ckpt && c->resid_deferred ? MH : 1);
+  return cv.off;
+}
+
+#define CKB(expr)                                                             \
+  do {                                                                        \
+    hipError_t e_ = (expr);                                                   \
+    if (e_ != hipSuccess) return cfail(c, e_, "opadpo_seq_logprobs_bwd");     \
+  } while (0)
+
+// gradient of the log-probs / entropies -> dX (fp32) and dXb (bf16) at the input of the final norm, scattered to the rows of the top layer
+static int head_bwd(opadpo_ctx* c, const opadpo_saved* sv, const BwdWs& w, const float* dlogp, const float* dent, hipStream_t st) {
+  const opadpo_dims& d = c->d;
+  const int R = sv->Rc, H = d.hidden, V = d.vocab, VC = sv->head_chunk;
+  const size_t MH = (size_t)sv->M * H;
+  if (sv->ragged) {      // gradients of the compact head rows: gathered from the rectangular [K,S,T] gradients (into d_hs, free until the norm backward)
+    float* dl_c = w.d_hs; float* de_c = w.d_hs + R;
+    hipLaunchKernelGGL(gather_cells_kernel, g1(R), dim3(256), 0, st, dlogp, dent, sv->cell, dl_c, de_c, R);
+    CKB(hipGetLastError());
+    dlogp = dl_c; if (dent) dent = de_c;
+  }
+  if (VC > 0) {
+    // per vocabulary chunk: recompute the logits (hn . W_c^T), dz_c from the row statistics of the forward, d_hn += dz_c . W_c (fp32
+    // accumulation across the chunks, ONE rounding to bf16 at the end - what the single K = vocab GEMM does inside its accumulators)
+    for (int c0 = 0; c0 < V; c0 += VC) {
+      const int n = std::min(VC, V - c0);
+      { GemmNTArgs g = gemm(sv->hn, H, c->lm_head + (size_t)c0 * H, H, H, sv->logits, VC, 1, R, n); CKB(run_gemm(c, g, st)); }
+      CKB(launch_head_bwd(sv->logits, VC, sv->labels, sv->lse_head, dlogp, dent ? sv->ent : nullptr, dent, 1.0f / sv->temperature, w.dz, VC, R, n, st, c0));
+      GemmNTArgs g = gemm(w.dz, VC, c->lm_head_t + c0, V, n, w.d_hn32, H, 1, R, H);
+      if (c0 > 0) resid(g, w.d_hn32, H, 1);
+      CKB(run_gemm(c, g, st));
+    }
+    CKB(launch_f32_to_bf16(w.d_hn32, w.d_hn, (size_t)R * H, st));
+  } else {
+    CKB(launch_head_bwd(sv->logits, V, sv->labels, sv->lse_head, dlogp, dent ? sv->ent : nullptr, dent, 1.0f / sv->temperature, w.dz, V, R, V, st));
+    GemmNTArgs g = gemm(w.dz, V, c->lm_head_t, V, V, w.d_hn, H, 0, R, H);
+    CKB(run_gemm(c, g, st));
+  }
+  CKB(launch_rmsnorm_bwd(w.d_hn, sv->hs, 1, c->norm, sv->rstd_f, nullptr, 0, w.d_hs, nullptr, R, H, st));
+  CKB(hipMemsetAsync(w.dX, 0, MH * sizeof(float), st));
+  // rows repeat: the last prefix row feeds token 0 of every response (ragged: compact head rows; with the compact top layer `rows` index the U rows that
+  // dX holds for that layer)
+  if (sv->K > 1 || sv->ragged) CKB(launch_scatter_add_rows_f32(w.d_hs, sv->rows, w.dX, H, R, H, st));
+  else CKB(launch_scatter_rows((const bf16_t*)w.d_hs, sv->rows, (bf16_t*)w.dX, 2 * H, R, 2 * H, st));
+  CKB(launch_f32_to_bf16(w.dX, w.dXb, MH, st));
+  return 0;
+}
+
+// ---- the "LoRA Linear" backward, in two halves (the q|k|v wgrad group launches between them).  A Linear y [rows, N] = x [rows, K] . W^T + (s . x~ . A^T) . B^T
+// of `groups` fused modules (lora_linear_fwd); a / b = offsets of its A / B blocks in the layer's flat LoRA buffer.
+// LoRA dropout (rate > 0 only): dA reads the regenerated masked input xm instead of x, and the dT . A term of the input gradient - masked element by
+// element - cannot be a K-tail of the dgrad product: it runs as its own product per module into du, lora_dropout_bwd_add adds it.
+struct LoraLinBwd {
+  const bf16_t* dY; int N, K, groups; size_t a, b;
+  const bf16_t* t;                  // the forward's s . x~ . A^T [rows, groups * r]
+  const bf16_t *x, *xm;             // the Linear's input; its masked copies (read with dropout only)
+  bf16_t* dT; int rows;
+  int module0; const int32_t* drop_rows;
+};
+// what the Linears of one layer's backward share: transposed LoRA weights and gradient of the layer, the wgrad group under collection, dropout
+struct LayerBwd { opadpo_ctx* c; hipStream_t st; int layer; const bf16_t* wt; float* gr; GemmTNArgs* wg; int nwg; const LoraDropout* dp; bf16_t* du; };
+
+// (a) dT = s . dY . B, and the dB = dY^T . t and dA = dT^T . x~ wgrads appended to the layer's group
+static hipError_t lora_linear_bwd_dt(LayerBwd& L, const LoraLinBwd& l) {
+  const opadpo_dims& d = L.c->d;
+  const int r = d.lora_r, g = l.groups, n = l.N / g;
+  const bool masked = L.dp != nullptr;
+  GemmNTArgs gt = gemm(l.dY, l.N, L.wt + l.b, n, n, l.dT, g * r, 0, l.rows, g * r);
+  gt.alpha = d.lora_alpha / d.lora_r;
+  if (g > 1) { gt.a1_group_n = r; gt.a1_group_stride = n; }
+  TRY(run_gemm(L.c, gt, L.st));
+  auto tn = [&](const bf16_t* P, int ldp, const bf16_t* Q, int ldq, float* C, int ldc, int N1, int N2, int qgn, int qgs) {
+    GemmTNArgs& t = L.wg[L.nwg++]; t.P = P; t.Q = Q; t.C = C; t.M = l.rows; t.N1 = N1; t.N2 = N2; t.ldp = ldp; t.ldq = ldq; t.ldc = ldc;
+    t.q_group_n1 = qgn; t.q_group_stride = qgs; t.alpha = 1.f; t.splits = 0;
+  };
+  tn(l.dY, l.N, l.t, g * r, L.gr + l.b, r, l.N, r, g > 1 ? n : 0, g > 1 ? r : 0);
+  const bool grouped = masked && g > 1;      // one masked copy per module, side by side
+  tn(l.dT, g * r, masked ? l.xm : l.x, grouped ? g * l.K : l.K, L.gr + l.a, l.K, g * r, l.K, grouped ? r : 0, grouped ? l.K : 0);
+  return hipSuccess;
+}
+// (b) dX = dY . W + dT . A: `g` is the base product dY . W as the call site decorated it (the SwiGLU-backward epilogue of the down projection)
+static hipError_t lora_linear_bwd_dx(LayerBwd& L, const LoraLinBwd& l, GemmNTArgs g) {
+  const int r = L.c->d.lora_r, n = l.groups;
+  if (!L.dp) { tail(g, l.dT, n * r, L.wt + l.a, n * r, n * r); return run_gemm(L.c, g, L.st); }
+  TRY(run_gemm(L.c, g, L.st));
+  for (int j = 0; j < n; ++j) {
+    GemmNTArgs gu = gemm(l.dT + j * r, n * r, L.wt + l.a + j * r, n * r, r, L.du + (size_t)j * l.K, n * l.K, 0, l.rows, l.K);
+    TRY(run_gemm(L.c, gu, L.st));
+  }
+  return launch_lora_dropout_bwd_add((bf16_t*)g.C, L.du, l.rows, l.K, n, *L.dp, L.layer, l.module0, l.drop_rows, L.st);
+}
+
+// backward of decoder layer i: dX / dXb (gradient of its output) -> the layer's 8 LoRA wgrads and, with need_dx, dX / dXb of its input
+static int layer_bwd(opadpo_ctx* c, opadpo_saved* sv, const opadpo_ctx::Adapter& ad, const BwdWs& ws, int i, bool need_dx, hipStream_t st) {
+  const opadpo_dims& d = c->d;
+  const int S = sv->S, Lp = sv->L, M = sv->M, H = d.hidden, F = d.ffn, nh = d.n_heads, hd = d.head_dim;
+  const size_t MH = (size_t)M * H;
+  const opadpo_layer_weights& w = c->layers[i];
+  if (!w.wqkv_t || !w.wo_t || !w.wgu_t || !w.wd_t) return cbad(c, "opadpo_seq_logprobs_bwd", "transposed base weights not set (needed by dgrad)");
+  const LoraOff o = lora_off(d);
+  const bool drop = sv->drop_on != 0;
+  const Rag rag{sv->meta, sv->meta_stride, sv->K, M, sv->row_pos};
+  const Rag* rg = sv->ragged ? &rag : nullptr;
+  // compact top layer (opadpo_saved::Uc): its MLP / o-projection activations and the incoming gradient are rows of U, not of the batch
+  const bool top = sv->Uc > 0 && i == d.n_layers - 1;
+  const int Mm = top ? sv->Uc : M;
+  const LayerBufs b = slot(d, sv, sv->ckpt ? 0 : i);
+  if (sv->ckpt) {                                   // the slot holds whatever layer ran last: re-run layer i from x_i with the forward's arguments
+    float* const xi = sv->x + (size_t)i * MH;
+    const TopRows top_rc{sv->urow, sv->Uc, sv->attn_u, ws.rc_xu};
+    const DropFwd drop_rc{sv->drop, sv->xm};
+    hipError_t e = layer_fwd(c, i, ad, xi, nullptr, xi, c->resid_deferred ? ws.rc_y : nullptr, b, S, Lp, sv->key_mask, sv->seg_prefix, sv->seg_len, nullptr, nullptr, 0,
+                             st, rg, top ? &top_rc : nullptr, drop ? &drop_rc : nullptr, true);
+    if (e != hipSuccess) return cfail(c, e, "opadpo_seq_logprobs_bwd (layer recompute)");
+  }
+  // the 8 LoRA wgrads of the layer are collected and run as ONE grouped launch (launch_gemm_tn_group) once the last of their
+  // operands exists: every operand stays untouched until then (dt_ra is the second dT buffer that makes that true)
+  GemmTNArgs wg[8];
+  LayerBwd L{c, st, i, ad.work_t + (size_t)i * o.layer, ad.grad + (size_t)i * o.layer, wg, 0, drop ? &sv->drop : nullptr, ws.du};
+  const int32_t* drows = top ? sv->urow : nullptr;       // compact top layer: its rows hash with their row of the pass
+  const bf16_t* attn_in = top ? sv->attn_u : b.attn;     // input of the o projection
+  if (drop) {
+    CKB(launch_lora_dropout_fwd(b.act, ws.xm_d, Mm, F, 1, sv->drop, i, 6, drows, st));
+    CKB(launch_lora_dropout_fwd(b.n2, ws.xm_gu, Mm, H, 2, sv->drop, i, 4, drows, st));
+    CKB(launch_lora_dropout_fwd(attn_in, ws.xm_o, Mm, H, 1, sv->drop, i, 3, drows, st));
+    CKB(launch_lora_dropout_fwd(b.n1, ws.xm_qkv, M, H, 3, sv->drop, i, 0, nullptr, st));
+  }
+  // ---- MLP ----
+  const LoraLinBwd down{ws.dXb, H, F, 1, o.a_d, o.b_d, b.t_d, b.act, ws.xm_d, ws.dt_r, Mm, 6, drows};
+  CKB(lora_linear_bwd_dt(L, down));
+  {
+    // SwiGLU backward in the dgrad's epilogue: d_act never reaches HBM.  Default since round 5 in the DIRECT form (gate / up operands requested one
+    // row block ahead of the accumulator read-out, lane-local math, gemm.hip w4_direct_epilogue_swiglu_bwd; context flag bit 14
+    // keeps the two-kernel form).  Flag bit 6 = the LDS-staged form of rounds 3-4 (every operand load's latency exposed: 1016.9 vs 1013.3 ms per step
+    // for the two-kernel form then) - the cross-check of the direct one.  Not with dropout: the masked dT . A term is added to d_act first.
+    const bool sb_staged = c->swiglu_bwd_staged;
+    const bool sb_fused = !drop && F % 256 == 0 && (sb_staged || !c->swiglu_bwd_own_kernel);
+    GemmNTArgs g = gemm(ws.dXb, H, w.wd_t, H, H, sb_fused ? ws.d_gu : ws.d_act, sb_fused ? 2 * F : F, 0, Mm, F);
+    if (sb_fused) { g.act = OPADPO_ACT_SWIGLU_BWD; g.R = b.gu; g.ldr = 2 * F; g.r_f32 = 0; g.swiglu_bwd_staged = sb_staged ? 1 : 0; }
+    CKB(lora_linear_bwd_dx(L, down, g));
+    if (!sb_fused) CKB(launch_silu_mul_bwd(ws.d_act, b.gu, ws.d_gu, Mm, F, st));
+  }
+  const LoraLinBwd gate_up{ws.d_gu, 2 * F, H, 2, o.a_gu, o.b_gu, b.t_gu, b.n2, ws.xm_gu, ws.dt_2r, Mm, 4, drows};
+  CKB(lora_linear_bwd_dt(L, gate_up));
+  CKB(lora_linear_bwd_dx(L, gate_up, gemm(ws.d_gu, 2 * F, w.wgu_t, 2 * F, 2 * F, ws.d_n, H, 0, Mm, H)));
+  CKB(launch_rmsnorm_bwd(ws.d_n, b.h, 1, w.ln2, b.rstd2, ws.dX, 1, ws.d_h, ws.d_hb, Mm, H, st));
+  // ---- attention ----
+  bf16_t* const d_ao = top ? ws.d_n : ws.d_attn;       // d_n is free again: the norm backward above has consumed it
+  const LoraLinBwd o_proj{ws.d_hb, H, H, 1, o.a_o, o.b_o, b.t_o, attn_in, ws.xm_o, ws.dt_ra, Mm, 3, drows};
+  CKB(lora_linear_bwd_dt(L, o_proj));
+  CKB(lora_linear_bwd_dx(L, o_proj, gemm(ws.d_hb, H, w.wo_t, H, H, d_ao, H, 0, Mm, H)));
+  if (top) {                                       // gradient of the attention output: U rows carry one, every other row zero
+    CKB(hipMemsetAsync(ws.d_attn, 0, MH * sizeof(bf16_t), st));
+    CKB(launch_scatter_rows(ws.d_n, sv->urow, ws.d_attn, H, Mm, H, st));
+  }
+  AttnArgs a = attn_args(d, b, sv->key_mask, S, Lp, sv->seg_prefix, sv->seg_len, rg);
+  a.dout = ws.d_attn; a.dq_acc = nullptr; a.dq = ws.dqkv; a.dk = ws.dqkv + H; a.dv = ws.dqkv + 2 * H; a.delta = ws.delta;
+  // ragged rows: dQ / dK leave the attention backward already rotated back (lane-local in its accumulator layout) - no pass over dq | dk;
+  // context flag bit 11 (and padded rows) keep the separate inverse rope kernel
+  const bool fuse_rope_bwd = sv->ragged && !c->rope_own_kernel;
+  if (fuse_rope_bwd) { a.rope_pos = sv->row_pos; a.rope_l2theta = log2f(d.rope_theta); }
+  CKB(launch_attn_bwd(a, ctx_flags(c), st));
+  if (!fuse_rope_bwd) CKB(launch_rope(ws.dqkv, 3 * H, c->cosb, c->sinb, M, Lp, 2 * nh, hd, 1, nullptr, sv->seg_prefix, sv->seg_len, st, sv->ragged ? sv->row_pos : nullptr,
+                                      sv->ragged ? log2f(d.rope_theta) : 0.f));
+  const LoraLinBwd qkv{ws.dqkv, 3 * H, H, 3, o.a_qkv, o.b_qkv, b.t_qkv, b.n1, ws.xm_qkv, ws.dt_3r, M, 0, nullptr};
+  CKB(lora_linear_bwd_dt(L, qkv));
+  { int ord = 1;      // what the launches of THIS list actually did (not a synthetic shape list): ordered reduce for every problem, or atomics somewhere
+    CKB(launch_gemm_tn_group(wg, L.nwg, ctx_flags(c), st, ws.tn_ws_floats > 1 ? ws.tn_ws : nullptr, ws.tn_ws_floats > 1 ? ws.tn_ws_floats * sizeof(float) : 0, &ord));
+    if (!ord) c->wgrad_det = 0; }
+  if (!need_dx) return 0;          // layer-0 input is the frozen embedding / image features: no further dgrad in the DPO stage
+  CKB(lora_linear_bwd_dx(L, qkv, gemm(ws.dqkv, 3 * H, w.wqkv_t, 3 * H, 3 * H, ws.d_n, H, 0, M, H)));
+  const float* dres = ws.d_h;
+  if (top) {                                       // residual gradient of the block: d_h holds it for the U rows only
+    CKB(hipMemsetAsync(ws.d_full, 0, MH * sizeof(float), st));
+    CKB(launch_scatter_rows((const bf16_t*)ws.d_h, sv->urow, (bf16_t*)ws.d_full, 2 * H, Mm, 2 * H, st));      // fp32 rows = 2H bf16 units
+    dres = ws.d_full;
+  }
+  CKB(launch_rmsnorm_bwd(ws.d_n, sv->x + (size_t)i * MH, 1, w.ln1, b.rstd1, dres, 1, ws.dX, ws.dXb, M, H, st));
+  return 0;
+}
+
+// splice backward (OPA LoRA-SFT stage): the image positions' rows of dX at the input of layer 0 -> d_feats
+static int splice_bwd(opadpo_ctx* c, const opadpo_saved* sv, const float* dX, float* d_feats, hipStream_t st) {
+  const opadpo_dims& d = c->d;
+  const int side = d.image_size / d.patch, P = side * side;
+  hipLaunchKernelGGL(splice_grad_kernel, dim3(P, sv->S), dim3(256), 0, st, dX, sv->ids, sv->feat_row, d_feats, sv->S, sv->n_txt, sv->L, P, d.hidden, OPADPO_IMAGE_TOKEN,
+                     sv->ragged ? sv->meta : nullptr, sv->meta_stride, sv->K);
+  CKB(hipGetLastError());
+  return 0;
+}
+#undef CKB
+
 // Layers [layer_lo, layer_hi] are processed top-down; the first call of a backward must start at layer_hi = n_layers - 1 (it runs
 // the head backward), later calls continue where the previous one stopped (the data-parallel host launches the exchange of a
 // finished bucket of layers between two calls).
@@ -1114,9 +1321,7 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
   const opadpo_ctx::Adapter& ad = c->adapters[sv->adapter];
   if (ad.kind != 1 || !ad.grad || !ad.work_t) return cbad(c, __func__, "adapter lost its gradient / transposed buffers");
   hipStream_t st = (hipStream_t)stream;
-  const int S = sv->S, Lp = sv->L, M = sv->M, R = sv->Rc, H = d.hidden, F = d.ffn, r = d.lora_r, nh = d.n_heads, hd = d.head_dim, V = d.vocab;
-  const float s = d.lora_alpha / d.lora_r;
-  const size_t MH = (size_t)M * H;
+  const int M = sv->M, H = d.hidden, F = d.ffn, r = d.lora_r;
   // workspace of the LoRA wgrads' deterministic flush (gemm_tn_w4_kernel writes a run's partial tiles there, gemm_tn_reduce_kernel adds them in a
   // fixed order: no fp32 atomics, gradients bit-reproducible run to run): the worst case over the layer's 8 problems as one group, or one
   // by one (compact top layer: two row counts); context flag (use_tr) bit 12 keeps the atomic flush (A/B)
@@ -1133,208 +1338,22 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
       tn_ws_floats = std::max(tn_ws_floats, gemm_tn_group_workspace_bytes(shp, 8, ctx_flags(c)) / sizeof(float));
     }
   }
-  // workspace (persists between the ranged calls of one backward)
-  size_t need = 0;
-  const int VC = sv->head_chunk;                      // chunked head: dz and the recomputed logits exist for one vocabulary chunk at a time
-  const size_t dz_cols = VC > 0 ? (size_t)VC : (size_t)V;
-  { Carve cv(nullptr); cv.take<bf16_t>((size_t)R * dz_cols); cv.take<float>(VC > 0 ? (size_t)R * H : 1); cv.take<bf16_t>((size_t)R * H); cv.take<float>((size_t)R * H); cv.take<float>(MH); cv.take<bf16_t>(MH);
-    cv.take<float>(MH); cv.take<bf16_t>(MH); cv.take<bf16_t>(MH); cv.take<bf16_t>((size_t)M * F); cv.take<bf16_t>((size_t)M * 2 * F); cv.take<bf16_t>(MH);
-    cv.take<bf16_t>((size_t)M * 3 * H); cv.take<float>((size_t)S * nh * Lp); cv.take<bf16_t>((size_t)M * r); cv.take<bf16_t>((size_t)M * 2 * r);
-    cv.take<bf16_t>((size_t)M * 3 * r); cv.take<bf16_t>((size_t)M * r); cv.take<float>(sv->Uc > 0 ? MH : 1); cv.take<float>(tn_ws_floats);
-    cv.take<bf16_t>(sv->drop_on ? (size_t)M * (F + 6 * H) : 0); cv.take<bf16_t>(sv->drop_on ? (size_t)M * std::max(3 * H, F) : 0);
-    cv.take<float>(sv->ckpt && sv->Uc > 0 ? (size_t)sv->Uc * H : 1); cv.take<float>(sv->ckpt && c->resid_deferred ? MH : 1); need = cv.off; }
+  BwdWs ws{};
+  const size_t need = bwd_layout(c, sv, tn_ws_floats, &ws, nullptr);
   const bool first = layer_hi == d.n_layers - 1;
   if (first) c->wgrad_det = 1;                        // of THIS backward: cleared below by any grouped wgrad launch that fell back to fp32 atomics
-  if (R == 0) return 0;                               // no valid response token: every gradient of this pass is exactly zero (nothing flushed: trivially reproducible)
+  if (sv->Rc == 0) return 0;                          // no valid response token: every gradient of this pass is exactly zero (nothing flushed: trivially reproducible)
   if (!first && (c->ws_bytes < need || !c->ws)) return cbad(c, __func__, "ranged backward must start at the top layer");
   void* base = ctx_ws(c, need, st);
   if (!base) return cfail(c, hipErrorOutOfMemory, __func__);
-  Carve cv(base);
-  bf16_t* dz = cv.take<bf16_t>((size_t)R * dz_cols); float* d_hn32 = cv.take<float>(VC > 0 ? (size_t)R * H : 1);
-  bf16_t* d_hn = cv.take<bf16_t>((size_t)R * H); float* d_hs = cv.take<float>((size_t)R * H);
-  float* dX = cv.take<float>(MH); bf16_t* dXb = cv.take<bf16_t>(MH); float* d_h = cv.take<float>(MH); bf16_t* d_hb = cv.take<bf16_t>(MH);
-  bf16_t* d_n = cv.take<bf16_t>(MH); bf16_t* d_act = cv.take<bf16_t>((size_t)M * F); bf16_t* d_gu = cv.take<bf16_t>((size_t)M * 2 * F);
-  bf16_t* d_attn = cv.take<bf16_t>(MH); bf16_t* dqkv = cv.take<bf16_t>((size_t)M * 3 * H); float* delta = cv.take<float>((size_t)S * nh * Lp);
-  bf16_t* dt_r = cv.take<bf16_t>((size_t)M * r); bf16_t* dt_2r = cv.take<bf16_t>((size_t)M * 2 * r); bf16_t* dt_3r = cv.take<bf16_t>((size_t)M * 3 * r);
-  bf16_t* dt_ra = cv.take<bf16_t>((size_t)M * r);        // dT of the o projection (dt_r keeps the down projection's until the grouped wgrad)
-  float* d_full = cv.take<float>(sv->Uc > 0 ? MH : 1);   // compact top layer: its residual gradient scattered back to every row
-  float* tn_ws = cv.take<float>(tn_ws_floats);
-  // LoRA dropout: the masked copies of the layer's four Linear inputs, regenerated from the saved activations ([down | gate, up | o | q, k, v]: they stay
-  // untouched until the grouped wgrad launch), and the un-fused dT . A products of one Linear
-  const bool drop = sv->drop_on != 0;
-  bf16_t* xm_d = cv.take<bf16_t>(drop ? (size_t)M * (F + 6 * H) : 0);
-  bf16_t* xm_gu = xm_d + (size_t)M * F; bf16_t* xm_o = xm_gu + (size_t)M * 2 * H; bf16_t* xm_qkv = xm_o + MH;
-  bf16_t* du = cv.take<bf16_t>(drop ? (size_t)M * std::max(3 * H, F) : 0);
-  // checkpointed pass: scratch of the recomputed layers - the gathered input of the compact top layer (the forward borrowed sv->hs, which the head
-  // backward owns by now) and, deferred-residual form only, the o projection's product.  Never a kept x slot.
-  float* rc_xu = cv.take<float>(sv->ckpt && sv->Uc > 0 ? (size_t)sv->Uc * H : 1);
-  float* rc_y = cv.take<float>(sv->ckpt && c->resid_deferred ? MH : 1);
-  const LoraDropout& dp = sv->drop;
-  const LoraOff o = lora_off(d);
-  const Rag rag{sv->meta, sv->meta_stride, sv->K, M, sv->row_pos};
-  const TopRows top_rc{sv->urow, sv->Uc, sv->attn_u, rc_xu};
-  const DropFwd drop_rc{sv->drop, sv->xm};
+  bwd_layout(c, sv, tn_ws_floats, &ws, base);
   if (first) {
     if (!dlogp) return cbad(c, __func__, "null dlogp");
-    if (sv->ragged && R > 0) {      // gradients of the compact head rows: gathered from the rectangular [K,S,T] gradients (into d_hs, free until the norm backward)
-      float* dl_c = d_hs; float* de_c = d_hs + R;
-      hipLaunchKernelGGL(gather_cells_kernel, g1(R), dim3(256), 0, st, dlogp, dent, sv->cell, dl_c, de_c, R);
-      CK(hipGetLastError());
-      dlogp = dl_c; if (dent) dent = de_c;
-    }
-    if (VC > 0) {
-      // per vocabulary chunk: recompute the logits (hn . W_c^T), dz_c from the row statistics of the forward, d_hn += dz_c . W_c (fp32
-      // accumulation across the chunks, ONE rounding to bf16 at the end - what the single K = vocab GEMM does inside its accumulators)
-      for (int c0 = 0; c0 < V; c0 += VC) {
-        const int n = std::min(VC, V - c0);
-        { GemmNTArgs g = gemm(sv->hn, H, c->lm_head + (size_t)c0 * H, H, H, sv->logits, VC, 1, R, n); CK(run_gemm(c, g, st)); }
-        CK(launch_head_bwd(sv->logits, VC, sv->labels, sv->lse_head, dlogp, dent ? sv->ent : nullptr, dent, 1.0f / sv->temperature, dz, VC, R, n, st, c0));
-        GemmNTArgs g = gemm(dz, VC, c->lm_head_t + c0, V, n, d_hn32, H, 1, R, H);
-        if (c0 > 0) resid(g, d_hn32, H, 1);
-        CK(run_gemm(c, g, st));
-      }
-      CK(launch_f32_to_bf16(d_hn32, d_hn, (size_t)R * H, st));
-    } else {
-      CK(launch_head_bwd(sv->logits, V, sv->labels, sv->lse_head, dlogp, dent ? sv->ent : nullptr, dent, 1.0f / sv->temperature, dz, V, R, V, st));
-      GemmNTArgs g = gemm(dz, V, c->lm_head_t, V, V, d_hn, H, 0, R, H);
-      CK(run_gemm(c, g, st));
-    }
-    CK(launch_rmsnorm_bwd(d_hn, sv->hs, 1, c->norm, sv->rstd_f, nullptr, 0, d_hs, nullptr, R, H, st));
-    CK(hipMemsetAsync(dX, 0, MH * sizeof(float), st));
-    if (sv->K > 1 || sv->ragged) CK(launch_scatter_add_rows_f32(d_hs, sv->rows, dX, H, R, H, st));     // rows repeat: the last prefix row feeds token 0 of every response (ragged: compact head rows; with the compact top layer `rows` index the U rows that dX holds for that layer)
-    else CK(launch_scatter_rows((const bf16_t*)d_hs, sv->rows, (bf16_t*)dX, 2 * H, R, 2 * H, st));
-    CK(launch_f32_to_bf16(dX, dXb, MH, st));
+    if (int e = head_bwd(c, sv, ws, dlogp, dent, st)) return e;
   }
-  for (int i = layer_hi; i >= layer_lo; --i) {
-    const opadpo_layer_weights& w = c->layers[i];
-    if (!w.wqkv_t || !w.wo_t || !w.wgu_t || !w.wd_t) return cbad(c, __func__, "transposed base weights not set (needed by dgrad)");
-    const bf16_t* wt = ad.work_t + (size_t)i * o.layer;
-    float* gr = ad.grad + (size_t)i * o.layer;
-    const LayerBufs b = slot(d, sv, sv->ckpt ? 0 : i);
-    if (sv->ckpt) {                                 // the slot holds whatever layer ran last: re-run layer i from x_i with the forward's arguments
-      float* const xi = sv->x + (size_t)i * MH;
-      hipError_t e = layer_fwd(c, i, ad, xi, nullptr, xi, c->resid_deferred ? rc_y : nullptr, b, S, Lp, sv->key_mask, sv->seg_prefix, sv->seg_len, nullptr, nullptr, 0,
-                               st, sv->ragged ? &rag : nullptr, (sv->Uc > 0 && i == d.n_layers - 1) ? &top_rc : nullptr, drop ? &drop_rc : nullptr, true);
-      if (e != hipSuccess) return cfail(c, e, "opadpo_seq_logprobs_bwd (layer recompute)");
-    }
-    // the 8 LoRA wgrads of the layer are collected and run as ONE grouped launch (launch_gemm_tn_group) once the last of their
-    // operands exists: every operand stays untouched until then (dt_ra is the second dT buffer that makes that true)
-    GemmTNArgs wg[8];
-    int nwg = 0;
-    // compact top layer (opadpo_saved::Uc): its MLP / o-projection activations and the incoming gradient are rows of U, not of the batch
-    const bool top = sv->Uc > 0 && i == d.n_layers - 1;
-    const int Mm = top ? sv->Uc : M;
-    auto tn = [&](const bf16_t* Pm, int ldp, const bf16_t* Q, int ldq, float* Cg, int ldc, int N1, int N2, int qgn, int qgs, int rows) {
-      GemmTNArgs& t = wg[nwg++]; t.P = Pm; t.Q = Q; t.C = Cg; t.M = rows; t.N1 = N1; t.N2 = N2; t.ldp = ldp; t.ldq = ldq; t.ldc = ldc;
-      t.q_group_n1 = qgn; t.q_group_stride = qgs; t.alpha = 1.f; t.splits = 0;
-      return hipSuccess;
-    };
-    // ---- MLP ----
-    // LoRA dropout (rate > 0 only; the else branches are the pass without it): dA reads the regenerated masked input, and the dT . A term of the input
-    // gradient - masked element by element - cannot be a K-tail of the dgrad product: it runs as its own product into du, lora_dropout_bwd_add adds it
-    const int32_t* drows = top ? sv->urow : nullptr;       // compact top layer: its rows hash with their row of the pass
-    if (drop) {
-      CK(launch_lora_dropout_fwd(b.act, xm_d, Mm, F, 1, dp, i, 6, drows, st));
-      CK(launch_lora_dropout_fwd(b.n2, xm_gu, Mm, H, 2, dp, i, 4, drows, st));
-      CK(launch_lora_dropout_fwd(top ? sv->attn_u : b.attn, xm_o, Mm, H, 1, dp, i, 3, drows, st));
-      CK(launch_lora_dropout_fwd(b.n1, xm_qkv, M, H, 3, dp, i, 0, nullptr, st));
-    }
-    { GemmNTArgs g = gemm(dXb, H, wt + o.b_d, H, H, dt_r, r, 0, Mm, r); g.alpha = s; CK(run_gemm(c, g, st)); }
-    CK(tn(dXb, H, b.t_d, r, gr + o.b_d, r, H, r, 0, 0, Mm));
-    CK(tn(dt_r, r, drop ? xm_d : b.act, F, gr + o.a_d, F, r, F, 0, 0, Mm));
-    const bool sb_staged = c->swiglu_bwd_staged;
-    if (drop) {
-      { GemmNTArgs g = gemm(dXb, H, w.wd_t, H, H, d_act, F, 0, Mm, F); CK(run_gemm(c, g, st)); }
-      { GemmNTArgs g = gemm(dt_r, r, wt + o.a_d, r, r, du, F, 0, Mm, F); CK(run_gemm(c, g, st)); }
-      CK(launch_lora_dropout_bwd_add(d_act, du, Mm, F, 1, dp, i, 6, drows, st));
-      CK(launch_silu_mul_bwd(d_act, b.gu, d_gu, Mm, F, st));
-    } else if (F % 256 == 0 && (sb_staged || !c->swiglu_bwd_own_kernel)) {
-      // SwiGLU backward in the dgrad's epilogue: d_act never reaches HBM.  Default since round 5 in the DIRECT form (gate / up operands requested one
-      // row block ahead of the accumulator read-out, lane-local math, gemm.hip w4_direct_epilogue_swiglu_bwd; context flag bit 14
-      // keeps the two-kernel form).  Flag bit 6 = the LDS-staged form of rounds 3-4 (every operand load's latency exposed: 1016.9 vs 1013.3 ms per step
-      // for the two-kernel form then) - the cross-check of the direct one.
-      GemmNTArgs g = gemm(dXb, H, w.wd_t, H, H, d_gu, 2 * F, 0, Mm, F); tail(g, dt_r, r, wt + o.a_d, r, r);
-      g.act = OPADPO_ACT_SWIGLU_BWD; g.R = b.gu; g.ldr = 2 * F; g.r_f32 = 0; g.swiglu_bwd_staged = sb_staged ? 1 : 0;
-      CK(run_gemm(c, g, st));
-    } else {
-      { GemmNTArgs g = gemm(dXb, H, w.wd_t, H, H, d_act, F, 0, Mm, F); tail(g, dt_r, r, wt + o.a_d, r, r); CK(run_gemm(c, g, st)); }
-      CK(launch_silu_mul_bwd(d_act, b.gu, d_gu, Mm, F, st));
-    }
-    { GemmNTArgs g = gemm(d_gu, 2 * F, wt + o.b_gu, F, F, dt_2r, 2 * r, 0, Mm, 2 * r); g.alpha = s; g.a1_group_n = r; g.a1_group_stride = F; CK(run_gemm(c, g, st)); }
-    CK(tn(d_gu, 2 * F, b.t_gu, 2 * r, gr + o.b_gu, r, 2 * F, r, F, r, Mm));
-    if (drop) {
-      CK(tn(dt_2r, 2 * r, xm_gu, 2 * H, gr + o.a_gu, H, 2 * r, H, r, H, Mm));
-      { GemmNTArgs g = gemm(d_gu, 2 * F, w.wgu_t, 2 * F, 2 * F, d_n, H, 0, Mm, H); CK(run_gemm(c, g, st)); }
-      for (int j = 0; j < 2; ++j) { GemmNTArgs g = gemm(dt_2r + j * r, 2 * r, wt + o.a_gu + j * r, 2 * r, r, du + (size_t)j * H, 2 * H, 0, Mm, H); CK(run_gemm(c, g, st)); }
-      CK(launch_lora_dropout_bwd_add(d_n, du, Mm, H, 2, dp, i, 4, drows, st));
-    } else {
-    CK(tn(dt_2r, 2 * r, b.n2, H, gr + o.a_gu, H, 2 * r, H, 0, 0, Mm));
-    { GemmNTArgs g = gemm(d_gu, 2 * F, w.wgu_t, 2 * F, 2 * F, d_n, H, 0, Mm, H); tail(g, dt_2r, 2 * r, wt + o.a_gu, 2 * r, 2 * r); CK(run_gemm(c, g, st)); }
-    }
-    CK(launch_rmsnorm_bwd(d_n, b.h, 1, w.ln2, b.rstd2, dX, 1, d_h, d_hb, Mm, H, st));
-    // ---- attention ----
-    { GemmNTArgs g = gemm(d_hb, H, wt + o.b_o, H, H, dt_ra, r, 0, Mm, r); g.alpha = s; CK(run_gemm(c, g, st)); }
-    CK(tn(d_hb, H, b.t_o, r, gr + o.b_o, r, H, r, 0, 0, Mm));
-    CK(tn(dt_ra, r, drop ? xm_o : top ? sv->attn_u : b.attn, H, gr + o.a_o, H, r, H, 0, 0, Mm));
-    {
-      bf16_t* dst = top ? d_n : d_attn;            // d_n is free again: the norm backward above has consumed it
-      GemmNTArgs g = gemm(d_hb, H, w.wo_t, H, H, dst, H, 0, Mm, H);
-      if (drop) {
-        CK(run_gemm(c, g, st));
-        { GemmNTArgs gu_ = gemm(dt_ra, r, wt + o.a_o, r, r, du, H, 0, Mm, H); CK(run_gemm(c, gu_, st)); }
-        CK(launch_lora_dropout_bwd_add(dst, du, Mm, H, 1, dp, i, 3, drows, st));
-      } else {
-      tail(g, dt_ra, r, wt + o.a_o, r, r); CK(run_gemm(c, g, st));
-      }
-      if (top) {                                   // gradient of the attention output: U rows carry one, every other row zero
-        CK(hipMemsetAsync(d_attn, 0, MH * sizeof(bf16_t), st));
-        CK(launch_scatter_rows(d_n, sv->urow, d_attn, H, Mm, H, st));
-      }
-    }
-    AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.q = b.qkv; a.k = b.qkv + H; a.v = b.qkv + 2 * H; a.o = b.attn; a.lse = b.lse; a.key_mask = sv->key_mask;
-    a.S = S; a.L = Lp; a.nh = nh; a.hd = hd; a.ld = 3 * H; a.ldo = H; a.causal = 1 | OPADPO_ATTN_SKIP_MASKED_Q; a.scale = 1.0f / sqrtf((float)hd);
-    a.dout = d_attn; a.dq_acc = nullptr; a.dq = dqkv; a.dk = dqkv + H; a.dv = dqkv + 2 * H; a.delta = delta;
-    a.seg_prefix = sv->seg_prefix; a.seg_len = sv->seg_len;
-    if (sv->ragged) { a.seq_meta = sv->meta; a.meta_stride = sv->meta_stride; a.n_seg = sv->K; a.rows_total = M; a.seg_prefix = 0; a.seg_len = 0; }
-    // ragged rows: dQ / dK leave the attention backward already rotated back (lane-local in its accumulator layout) - no pass over dq | dk;
-    // context flag bit 11 (and padded rows) keep the separate inverse rope kernel
-    const bool fuse_rope_bwd = sv->ragged && !c->rope_own_kernel;
-    if (fuse_rope_bwd) { a.rope_pos = sv->row_pos; a.rope_l2theta = log2f(d.rope_theta); }
-    CK(launch_attn_bwd(a, ctx_flags(c), st));
-    if (!fuse_rope_bwd) CK(launch_rope(dqkv, 3 * H, c->cosb, c->sinb, M, Lp, 2 * nh, hd, 1, nullptr, sv->seg_prefix, sv->seg_len, st, sv->ragged ? sv->row_pos : nullptr,
-                                       sv->ragged ? log2f(d.rope_theta) : 0.f));
-    { GemmNTArgs g = gemm(dqkv, 3 * H, wt + o.b_qkv, H, H, dt_3r, 3 * r, 0, M, 3 * r); g.alpha = s; g.a1_group_n = r; g.a1_group_stride = H; CK(run_gemm(c, g, st)); }
-    CK(tn(dqkv, 3 * H, b.t_qkv, 3 * r, gr + o.b_qkv, r, 3 * H, r, H, r, M));
-    if (drop) CK(tn(dt_3r, 3 * r, xm_qkv, 3 * H, gr + o.a_qkv, H, 3 * r, H, r, H, M));
-    else CK(tn(dt_3r, 3 * r, b.n1, H, gr + o.a_qkv, H, 3 * r, H, 0, 0, M));
-    { int ord = 1;      // what the launches of THIS list actually did (not a synthetic shape list): ordered reduce for every problem, or atomics somewhere
-      CK(launch_gemm_tn_group(wg, nwg, ctx_flags(c), st, tn_ws_floats > 1 ? tn_ws : nullptr, tn_ws_floats > 1 ? tn_ws_floats * sizeof(float) : 0, &ord));
-      if (!ord) c->wgrad_det = 0; }
-    if (i > 0 || d_feats) {          // layer-0 input is the frozen embedding / image features: no further dgrad in the DPO stage
-      if (drop) {
-        { GemmNTArgs g = gemm(dqkv, 3 * H, w.wqkv_t, 3 * H, 3 * H, d_n, H, 0, M, H); CK(run_gemm(c, g, st)); }
-        for (int j = 0; j < 3; ++j) { GemmNTArgs g = gemm(dt_3r + j * r, 3 * r, wt + o.a_qkv + j * r, 3 * r, r, du + (size_t)j * H, 3 * H, 0, M, H); CK(run_gemm(c, g, st)); }
-        CK(launch_lora_dropout_bwd_add(d_n, du, M, H, 3, dp, i, 0, nullptr, st));
-      } else {
-      { GemmNTArgs g = gemm(dqkv, 3 * H, w.wqkv_t, 3 * H, 3 * H, d_n, H, 0, M, H); tail(g, dt_3r, 3 * r, wt + o.a_qkv, 3 * r, 3 * r); CK(run_gemm(c, g, st)); }
-      }
-      const float* dres = d_h;
-      if (top) {                                   // residual gradient of the block: d_h holds it for the U rows only
-        CK(hipMemsetAsync(d_full, 0, MH * sizeof(float), st));
-        CK(launch_scatter_rows((const bf16_t*)d_h, sv->urow, (bf16_t*)d_full, 2 * H, Mm, 2 * H, st));      // fp32 rows = 2H bf16 units
-        dres = d_full;
-      }
-      CK(launch_rmsnorm_bwd(d_n, sv->x + (size_t)i * MH, 1, w.ln1, b.rstd1, dres, 1, dX, dXb, M, H, st));
-    }
-  }
-  if (layer_lo == 0 && d_feats) {
-    const int side = d.image_size / d.patch, P = side * side;
-    hipLaunchKernelGGL(splice_grad_kernel, dim3(P, S), dim3(256), 0, st, dX, sv->ids, sv->feat_row, d_feats, S, sv->n_txt, Lp, P, H, OPADPO_IMAGE_TOKEN,
-                       sv->ragged ? sv->meta : nullptr, sv->meta_stride, sv->K);
-    CK(hipGetLastError());
-  }
+  for (int i = layer_hi; i >= layer_lo; --i)
+    if (int e = layer_bwd(c, sv, ad, ws, i, i > 0 || d_feats, st)) return e;
+  if (layer_lo == 0 && d_feats) return splice_bwd(c, sv, ws.dX, d_feats, st);
   return 0;
 }
 
@@ -1344,29 +1363,23 @@ static hipError_t decode_head(opadpo_ctx* c, const float* src_f32, const float* 
   opadpo_ctx::Decode& D = c->dec;
   const opadpo_dims& d = c->d;
   if (rows < 0) rows = D.B;
-  hipError_t e;
-  if (n_partials > 0) {
-    if ((e = launch_rmsnorm_sum_fwd(src_f32, 1, partials, n_partials, (size_t)D.B * d.hidden, c->norm, D.x2, D.hn, D.rstd, rows, d.hidden, d.rms_eps, st)) != hipSuccess) return e;
-  } else if ((e = launch_rmsnorm_fwd(src_f32, 1, c->norm, D.hn, D.rstd, rows, d.hidden, d.rms_eps, st)) != hipSuccess) return e;
+  if (n_partials > 0) TRY(launch_rmsnorm_sum_fwd(src_f32, 1, partials, n_partials, (size_t)D.B * d.hidden, c->norm, D.x2, D.hn, D.rstd, rows, d.hidden, d.rms_eps, st));
+  else TRY(launch_rmsnorm_fwd(src_f32, 1, c->norm, D.hn, D.rstd, rows, d.hidden, d.rms_eps, st));
   GemmNTArgs g = gemm(D.hn, d.hidden, c->lm_head, d.hidden, d.hidden, D.logits, d.vocab, 1, rows, d.vocab); g.act |= OPADPO_GEMM_STREAM;
-  if (D.use64 && rows == D.B) e = launch_gemm_nt_dec64(g, 1, 1, ctx_flags(c), st);
-  else e = run_gemm(c, g, st);
-  if (e != hipSuccess) return e;
+  TRY(D.use64 && rows == D.B ? launch_gemm_nt_dec64(g, 1, 1, ctx_flags(c), st) : run_gemm(c, g, st));
   if (D.beams) {
-    if ((e = launch_beam_step(D.logits, d.vocab, rows == D.B ? 1 : D.beams, D.items, D.beams, d.vocab, D.max_new, D.eos_id, D.pad_id, D.step_d, 0, D.bs,
-                              st)) != hipSuccess) return e;
+    TRY(launch_beam_step(D.logits, d.vocab, rows == D.B ? 1 : D.beams, D.items, D.beams, d.vocab, D.max_new, D.eos_id, D.pad_id, D.step_d, 0, D.bs, st));
     hipLaunchKernelGGL(add_i32_kernel, dim3(1), dim3(64), 0, st, D.step_d, 1);
     return hipGetLastError();
   }
-  if (!D.logit.bias_ids.empty() &&      // HF order: logits processors (the bias) before the warpers (temperature / top-k / top-p in the sampler)
-      (e = launch_logit_bias_add(D.logits, d.vocab, D.B, d.vocab, D.bias_ids, D.bias, D.logit.bias_ids.data(), (int)D.logit.bias_ids.size(), st)) != hipSuccess)
-    return e;
+  if (!D.logit.bias_ids.empty())      // HF order: logits processors (the bias) before the warpers (temperature / top-k / top-p in the sampler)
+    TRY(launch_logit_bias_add(D.logits, d.vocab, D.B, d.vocab, D.bias_ids, D.bias, D.logit.bias_ids.data(), (int)D.logit.bias_ids.size(), st));
   if (D.suppress_eos) {
     hipLaunchKernelGGL(set_column_f32_kernel, g1(D.B), dim3(256), 0, st, D.logits, d.vocab, D.B, D.eos_id, -INFINITY);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    TRY(hipGetLastError());
   }
-  if ((e = launch_sample(D.logits, d.vocab, D.B, d.vocab, D.temperature, D.top_k, D.top_p, D.seed, 0, D.step_d, D.finished, D.pad_id,
-                         D.suppress_eos ? -1 : D.eos_id, D.cur_tok, D.history, st)) != hipSuccess) return e;
+  TRY(launch_sample(D.logits, d.vocab, D.B, d.vocab, D.temperature, D.top_k, D.top_p, D.seed, 0, D.step_d, D.finished, D.pad_id,
+                    D.suppress_eos ? -1 : D.eos_id, D.cur_tok, D.history, st));
   hipLaunchKernelGGL(add_i32_kernel, dim3(1), dim3(64), 0, st, D.step_d, 1);
   return hipGetLastError();
 }
@@ -1374,28 +1387,27 @@ static hipError_t decode_head(opadpo_ctx* c, const float* src_f32, const float* 
 static hipError_t decode_one(opadpo_ctx* c, hipStream_t st) {
   opadpo_ctx::Decode& D = c->dec;
   const opadpo_dims& d = c->d;
-  const int B = D.B, H = d.hidden, r = d.lora_r, nh = d.n_heads, hd = d.head_dim;
-  const float s = d.lora_alpha / d.lora_r;
+  const int B = D.B, H = d.hidden, nh = d.n_heads, hd = d.head_dim;
   const opadpo_ctx::Adapter& ad = c->adapters[D.adapter];
   const LoraOff o = lora_off(d);
-  hipError_t e;
+  const LayerBufs& b = D.b;
   // layer i's decode attention: one cache per row, or (beam decode) the items' prefix caches + the rows' suffix caches through the slot table
   auto attn = [&](int i) -> hipError_t {
     const float scale = 1.0f / sqrtf((float)hd);
     if (D.beams) {
       const size_t pre = (size_t)D.items * nh * D.Lp * hd, suf = (size_t)B * nh * D.max_new * hd;
-      return launch_attn_decode_beam(D.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * pre, D.vc + i * pre, D.ks + i * suf, D.vs + i * suf, D.att, D.key_mask,
+      return launch_attn_decode_beam(b.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * pre, D.vc + i * pre, D.ks + i * suf, D.vs + i * suf, b.attn, D.key_mask,
                                      D.items, D.beams, nh, hd, D.pos_d, D.Lp, D.max_new, D.bs.table, D.bs.table_stride, scale, D.ws, D.ws_bytes, st);
     }
     const size_t per_layer = (size_t)B * nh * D.max_ctx * hd;
-    return launch_attn_decode_fused(D.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * per_layer, D.vc + i * per_layer, D.att, D.key_mask, B, nh, hd, D.pos_d,
+    return launch_attn_decode_fused(b.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * per_layer, D.vc + i * per_layer, b.attn, D.key_mask, B, nh, hd, D.pos_d,
                                     D.max_ctx, scale, D.ws, D.ws_bytes, st);
   };
   hipLaunchKernelGGL(add_i32_kernel, dim3(1), dim3(64), 0, st, D.pos_d, 1);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  if ((e = launch_gather_rows(c->embed, H, D.cur_tok, D.emb, B, H, st)) != hipSuccess) return e;
+  TRY(hipGetLastError());
+  TRY(launch_gather_rows(c->embed, H, D.cur_tok, D.emb, B, H, st));
   if (D.use64) {
-    // 9..64 tokens: the decode GEMMs for <= 64 tokens (opadpo_gemm_nt_decode); x / hb = fp32 residual stream, part_o / part_d = K-slice partial tiles of the o / down
+    // 9..64 tokens: the decode GEMMs for <= 64 tokens (opadpo_gemm_nt_decode); x / b.h = fp32 residual stream, part_o / part_d = K-slice partial tiles of the o / down
     // projections, added (in slice order) by the RMSNorm that follows them
     const int F = d.ffn;
     const size_t pstride = (size_t)B * H;
@@ -1406,52 +1418,35 @@ static hipError_t decode_one(opadpo_ctx* c, hipStream_t st) {
     for (int i = 0; i < d.n_layers; ++i) {
       const opadpo_layer_weights& w0 = c->layers[i];
       const opadpo_layer_weights& w = ad.kind == 2 ? ad.merged[i] : w0;
-      if (i == 0) e = launch_rmsnorm_sum_fwd(D.emb, 0, nullptr, 0, 0, w0.ln1, D.x, D.n1, D.rstd, B, H, d.rms_eps, st);
-      else e = launch_rmsnorm_sum_fwd(D.hb, 1, D.part_d, D.split_d, pstride, w0.ln1, D.x, D.n1, D.rstd, B, H, d.rms_eps, st);
-      if (e != hipSuccess) return e;
-      if ((e = dg(D.n1, H, w.wqkv, H, D.qkv, 3 * H, 3 * H, 0, 1)) != hipSuccess) return e;
-      if ((e = attn(i)) != hipSuccess) return e;
-      if ((e = dg(D.att, H, w.wo, H, D.part_o, H, H, 1, D.split_o)) != hipSuccess) return e;
-      if ((e = launch_rmsnorm_sum_fwd(D.x, 1, D.part_o, D.split_o, pstride, w0.ln2, D.hb, D.n2, D.rstd, B, H, d.rms_eps, st)) != hipSuccess) return e;
+      if (i == 0) TRY(launch_rmsnorm_sum_fwd(D.emb, 0, nullptr, 0, 0, w0.ln1, D.x, b.n1, D.rstd, B, H, d.rms_eps, st));
+      else TRY(launch_rmsnorm_sum_fwd(b.h, 1, D.part_d, D.split_d, pstride, w0.ln1, D.x, b.n1, D.rstd, B, H, d.rms_eps, st));
+      TRY(dg(b.n1, H, w.wqkv, H, b.qkv, 3 * H, 3 * H, 0, 1));
+      TRY(attn(i));
+      TRY(dg(b.attn, H, w.wo, H, D.part_o, H, H, 1, D.split_o));
+      TRY(launch_rmsnorm_sum_fwd(D.x, 1, D.part_o, D.split_o, pstride, w0.ln2, b.h, b.n2, D.rstd, B, H, d.rms_eps, st));
       if (ad.kind == 2 && ad.swiglu_pair) {
-        if ((e = dg(D.n2, H, w.wgu, H, D.act, F, 2 * F, 2, 1)) != hipSuccess) return e;
+        TRY(dg(b.n2, H, w.wgu, H, b.act, F, 2 * F, 2, 1));
       } else {
-        if ((e = dg(D.n2, H, w.wgu, H, D.gu, 2 * F, 2 * F, 0, 1)) != hipSuccess) return e;
-        if ((e = launch_silu_mul_fwd(D.gu, D.act, B, F, st)) != hipSuccess) return e;
+        TRY(dg(b.n2, H, w.wgu, H, b.gu, 2 * F, 2 * F, 0, 1));
+        TRY(launch_silu_mul_fwd(b.gu, b.act, B, F, st));
       }
-      if ((e = dg(D.act, F, w.wd, F, D.part_d, H, H, 1, D.split_d)) != hipSuccess) return e;
+      TRY(dg(b.act, F, w.wd, F, D.part_d, H, H, 1, D.split_d));
     }
-    return decode_head(c, D.hb, D.part_d, D.split_d, st);
+    return decode_head(c, b.h, D.part_d, D.split_d, st);
   }
   const void* cur = D.emb; int cur_f32 = 0;
   float* nx = D.x;
-  LayerBufs b; b.n1 = D.n1; b.qkv = D.qkv; b.t_qkv = D.t_qkv; b.attn = D.att; b.t_o = D.t_o; b.n2 = D.n2; b.t_gu = D.t_gu; b.gu = D.gu; b.act = D.act;
-  b.t_d = D.t_d; b.rstd1 = D.rstd; b.rstd2 = D.rstd; b.lse = nullptr; b.h = D.hb;
   for (int i = 0; i < d.n_layers; ++i) {
     const opadpo_layer_weights& w0 = c->layers[i];
     const opadpo_layer_weights& w = ad.kind == 2 ? ad.merged[i] : w0;
     const bf16_t* lw = ad.kind == 1 ? ad.work + (size_t)i * o.layer : nullptr;
-    if ((e = launch_rmsnorm_fwd(cur, cur_f32, w0.ln1, D.n1, D.rstd, B, H, d.rms_eps, st)) != hipSuccess) return e;
-    if (lw) {
-      GemmNTArgs g1_ = gemm(D.n1, H, lw + o.a_qkv, H, H, D.t_qkv, 3 * r, 0, B, 3 * r); g1_.alpha = s; g1_.act |= OPADPO_GEMM_STREAM;
-      if ((e = run_gemm(c, g1_, st)) != hipSuccess) return e;
-      GemmNTArgs g2 = gemm(D.n1, H, w.wqkv, H, H, D.qkv, 3 * H, 0, B, 3 * H); tail(g2, D.t_qkv, 3 * r, lw + o.b_qkv, r, r, H, r); g2.act |= OPADPO_GEMM_STREAM;
-      if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
-    } else {
-      GemmNTArgs g2 = gemm(D.n1, H, w.wqkv, H, H, D.qkv, 3 * H, 0, B, 3 * H); g2.act |= OPADPO_GEMM_STREAM;
-      if ((e = run_gemm(c, g2, st)) != hipSuccess) return e;
-    }
-    if ((e = attn(i)) != hipSuccess) return e;
-    if (lw) {
-      GemmNTArgs g3 = gemm(D.att, H, lw + o.a_o, H, H, D.t_o, r, 0, B, r); g3.alpha = s; g3.act |= OPADPO_GEMM_STREAM;
-      if ((e = run_gemm(c, g3, st)) != hipSuccess) return e;
-      GemmNTArgs g4 = gemm(D.att, H, w.wo, H, H, D.hb, H, 1, B, H); tail(g4, D.t_o, r, lw + o.b_o, r, r); resid(g4, cur, H, cur_f32); g4.act |= OPADPO_GEMM_STREAM;
-      if ((e = run_gemm(c, g4, st)) != hipSuccess) return e;
-    } else {
-      GemmNTArgs g4 = gemm(D.att, H, w.wo, H, H, D.hb, H, 1, B, H); resid(g4, cur, H, cur_f32); g4.act |= OPADPO_GEMM_STREAM;
-      if ((e = run_gemm(c, g4, st)) != hipSuccess) return e;
-    }
-    if ((e = mlp_fwd(c, i, ad, D.hb, nx, b, B, OPADPO_GEMM_STREAM, st)) != hipSuccess) return e;
+    TRY(launch_rmsnorm_fwd(cur, cur_f32, w0.ln1, b.n1, D.rstd, B, H, d.rms_eps, st));
+    GemmNTArgs gq = gemm(b.n1, H, w.wqkv, H, H, b.qkv, 3 * H, 0, B, 3 * H); gq.act |= OPADPO_GEMM_STREAM;
+    TRY(lora_linear_fwd(c, i, gq, {lw, o.a_qkv, o.b_qkv, 3, b.t_qkv, 0, nullptr}, nullptr, st));
+    TRY(attn(i));
+    GemmNTArgs go = gemm(b.attn, H, w.wo, H, H, b.h, H, 1, B, H); resid(go, cur, H, cur_f32); go.act |= OPADPO_GEMM_STREAM;
+    TRY(lora_linear_fwd(c, i, go, {lw, o.a_o, o.b_o, 1, b.t_o, 3, nullptr}, nullptr, st));
+    TRY(mlp_fwd(c, i, ad, b.h, nx, b, B, OPADPO_GEMM_STREAM, st));
     cur = nx; cur_f32 = 1;
     nx = (nx == D.x) ? D.x2 : D.x;
   }
@@ -1494,10 +1489,11 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
       s.bp = cv.take<int32_t>(2 * (size_t)max_new_tokens * B); s.table_stride = (long long)B * max_new_tokens; s.table = cv.take<int32_t>(2 * (size_t)s.table_stride);
     }
     D.x = cv.take<float>((size_t)B * H); D.x2 = cv.take<float>((size_t)B * H); D.hs = cv.take<float>((size_t)B * H); D.hn = cv.take<bf16_t>((size_t)B * H);
-    D.n1 = cv.take<bf16_t>((size_t)B * H); D.qkv = cv.take<bf16_t>((size_t)B * 3 * H); D.t_qkv = cv.take<bf16_t>((size_t)B * 3 * r);
-    D.att = cv.take<bf16_t>((size_t)B * H); D.t_o = cv.take<bf16_t>((size_t)B * r); D.hb = cv.take<float>((size_t)B * H); D.n2 = cv.take<bf16_t>((size_t)B * H);
-    D.t_gu = cv.take<bf16_t>((size_t)B * 2 * r); D.gu = cv.take<bf16_t>((size_t)B * 2 * F); D.act = cv.take<bf16_t>((size_t)B * F); D.t_d = cv.take<bf16_t>((size_t)B * r);
-    D.rstd = cv.take<float>(B); D.emb = cv.take<bf16_t>((size_t)B * H); D.logits = cv.take<float>((size_t)B * V);
+    LayerBufs& b = D.b;
+    b.n1 = cv.take<bf16_t>((size_t)B * H); b.qkv = cv.take<bf16_t>((size_t)B * 3 * H); b.t_qkv = cv.take<bf16_t>((size_t)B * 3 * r);
+    b.attn = cv.take<bf16_t>((size_t)B * H); b.t_o = cv.take<bf16_t>((size_t)B * r); b.h = cv.take<float>((size_t)B * H); b.n2 = cv.take<bf16_t>((size_t)B * H);
+    b.t_gu = cv.take<bf16_t>((size_t)B * 2 * r); b.gu = cv.take<bf16_t>((size_t)B * 2 * F); b.act = cv.take<bf16_t>((size_t)B * F); b.t_d = cv.take<bf16_t>((size_t)B * r);
+    D.rstd = b.rstd1 = b.rstd2 = cv.take<float>(B); b.lse = nullptr; D.emb = cv.take<bf16_t>((size_t)B * H); D.logits = cv.take<float>((size_t)B * V);
     D.cur_tok = cv.take<int32_t>(B); D.finished = cv.take<uint8_t>(B); D.step_d = cv.take<int32_t>(1); D.pos_d = cv.take<int32_t>(1);
     D.ws = cv.take<uint8_t>(std::max<size_t>(D.ws_bytes, 4));
     D.part_o = cv.take<float>(D.use64 ? (size_t)D.split_o * B * H : 1);
@@ -1518,10 +1514,8 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
   size_t pbytes = 0;
   auto playout = [&](void* base) {
     Carve cv(base);
-    pf.x = cv.take<float>(3 * (size_t)M * H); pf.n1 = cv.take<bf16_t>((size_t)M * H); pf.rstd1 = cv.take<float>(M); pf.qkv = cv.take<bf16_t>((size_t)M * 3 * H);
-    pf.t_qkv = cv.take<bf16_t>((size_t)M * 3 * r); pf.attn = cv.take<bf16_t>((size_t)M * H); pf.lse = cv.take<float>((size_t)items * nh * Lp);
-    pf.t_o = cv.take<bf16_t>((size_t)M * r); pf.h = cv.take<float>((size_t)M * H); pf.n2 = cv.take<bf16_t>((size_t)M * H); pf.rstd2 = cv.take<float>(M);
-    pf.t_gu = cv.take<bf16_t>((size_t)M * 2 * r); pf.gu = cv.take<bf16_t>((size_t)M * 2 * F); pf.act = cv.take<bf16_t>((size_t)M * F); pf.t_d = cv.take<bf16_t>((size_t)M * r);
+    pf.x = cv.take<float>(3 * (size_t)M * H);
+    pf.lb = carve_layer_bufs(cv, d, 1, M, items, Lp);
     pf.key_mask = cv.take<uint8_t>((size_t)items * Lp); pf.rows = cv.take<int32_t>(items);
     pf.labels = cv.take<int32_t>(items);          // reused as feat_row = arange(items): every prompt carries its own image
     return cv.off;
@@ -1559,8 +1553,8 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
   CKD(hipGetLastError());
   if (fr) CKD(launch_gather_rows((const bf16_t*)xin, 2 * H, pf.rows, (bf16_t*)D.hs, items, 2 * H, st));   // last position of the last layer's output
   else {
-  CKD(launch_gather_rows((const bf16_t*)pb.h, 2 * H, pf.rows, (bf16_t*)D.hs, items, 2 * H, st));          // last position: x = h + y, added by the head's norm
-  CKD(launch_gather_rows((const bf16_t*)Yp, 2 * H, pf.rows, (bf16_t*)D.x, items, 2 * H, st));
+    CKD(launch_gather_rows((const bf16_t*)pb.h, 2 * H, pf.rows, (bf16_t*)D.hs, items, 2 * H, st));        // last position: x = h + y, added by the head's norm
+    CKD(launch_gather_rows((const bf16_t*)Yp, 2 * H, pf.rows, (bf16_t*)D.x, items, 2 * H, st));
   }
   CKD(hipMemsetAsync(D.finished, 0, beams ? items : B, st));
   CKD(hipMemsetAsync(D.step_d, 0, sizeof(int32_t), st));
@@ -1759,3 +1753,4 @@ int opadpo_decode_end(opadpo_ctx* c) {
 }
 
 }  // extern "C"
+#undef TRY

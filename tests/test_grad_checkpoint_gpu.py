@@ -22,6 +22,7 @@ pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 SEED = 77
 
+# tools/ctx_bits.py (parent / tree fingerprints of the context engine) imports GEOM, VARIANTS, _model, _pass and _peak from this module: keep the names
 TINY = dict(ffn=512, lora_r=256, lora_alpha=512.0)            # lora_r % 256 == 0: every wgrad on the kernel with the ordered flush
 WIDE = dict(hidden=4096, n_layers=2, n_heads=32, head_dim=128, ffn=11008, vocab=32000, v_hidden=128, v_layers=2, v_heads=2, v_ffn=256,
             lora_r=256, lora_alpha=512.0)                     # two decoder layers of LLaVA-1.5-7B width

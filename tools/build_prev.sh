@@ -9,8 +9,10 @@ T=$(mktemp -d)
 mkdir -p $T/a/csrc $T/include      # kernels.h includes ../../include/opadpo_hip.h
 for f in $(git -C $R ls-tree --name-only $REV opa-dpo_amd/csrc/); do git -C $R show $REV:$f > $T/a/csrc/$(basename $f); done
 git -C $R show $REV:include/opadpo_hip.h > $T/include/opadpo_hip.h
+mkdir -p $R/opa-dpo_amd/lib
 OBJS=""
-for s in gemm attention elementwise head_optim decode capi ctx; do
+for s in gemm attention elementwise dropout head_optim decode capi ctx; do
+  [ -f $T/a/csrc/$s.hip ] || continue      # a revision from before the file existed
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result "$@" -c $T/a/csrc/$s.hip -o $T/$s.o &
   OBJS="$OBJS $T/$s.o"
 done
