@@ -108,6 +108,15 @@ int opadpo_gemm_nt_rope_pos(const uint16_t* A1, int lda1, const uint16_t* B1, in
 int opadpo_gemm_nt_decode(const uint16_t* A, int lda, const uint16_t* B, int ldb, int K, void* C, int ldc, int mode, int M, int N, int splits,
                           void* stream);
 int opadpo_gemm_nt_decode_splits(int N, int K, int splits);
+/* The same projection for 65 <= M <= 256 tokens (rollout at 65..256 sequences per device): arguments, modes, `splits` and the shape rules of
+ * opadpo_gemm_nt_decode - N % 128 == 0, K % 64 == 0, lda / ldb % 8 == 0, ldc % 4 == 0 - with M in 65..256; a bad shape returns text and launches
+ * nothing.  A weight stream too (gemm_nt_decw_kernel): a workgroup owns 48 / 64 / 96 / 128 weight rows (by shape) x one K-slice, loads them global ->
+ * registers in whole 128-byte lines exactly once per launch, and uses each k-tile's operand against ceil(M / 64) groups of 64 token rows staged through LDS
+ * (two stages of 64 * groups rows x 128 deep).  The K-split is opadpo_gemm_nt_decode_splits(N, K, splits) - a function of (N, K) alone - and every output
+ * element is summed in the k order of the <= 64-token kernel: row i of the result is bit-identical for every M that contains it, and to what
+ * opadpo_gemm_nt_decode computes for that row. */
+int opadpo_gemm_nt_decode_wide(const uint16_t* A, int lda, const uint16_t* B, int ldb, int K, void* C, int ldc, int mode, int M, int N, int splits,
+                               void* stream);
 /* x_out = resid + sum_s partials[s] (fp32 [rows,H]; resid fp32 or bf16), y (nullable) = RMSNorm(x_out) * w in bf16, rstd (nullable):
  * the residual add + LlamaRMSNorm behind a K-split decode projection; fixed summation order (deterministic). */
 int opadpo_rmsnorm_sum_fwd(const void* resid, int resid_f32, const float* partials, int n_partials, size_t partial_stride, const uint16_t* w,
@@ -463,7 +472,12 @@ int opadpo_saved_residual(opadpo_ctx* ctx, const opadpo_saved* saved, int layer,
 
 /* policy.generate(do_sample=True, ...) (online_generator.py:292-309): prefill of B left-padded queries [B,Q] + token 0; the KV
  * cache ([n_layers, B, heads, Q+575+max_new_tokens, head_dim] x2) lives in the context.  history [max_new_tokens, B] int32
- * (caller-owned) receives the tokens; finished rows emit pad_id.  suppress_eos: benchmarks (never sample EOS). */
+ * (caller-owned) receives the tokens; finished rows emit pad_id.  suppress_eos: benchmarks (never sample EOS).
+ * 1 <= B <= 256 (above: refused with text).  Without LoRA tails (adapter-free or merged adapter) 9..64 rows decode on opadpo_gemm_nt_decode's kernel and
+ * 65..256 rows on opadpo_gemm_nt_decode_wide's, same layer shape.  An UNMERGED adapter with B > 64 is accepted and correct but unoptimised: its
+ * projections with their LoRA tails run on the tiled gemm_nt kernels (no weight-streaming kernel takes more than 64 rows with a tail) - merge the
+ * adapter (opadpo_ctx_set_merged_adapter) for a rollout of that size.  The prefill of B > 64 queries runs in groups of 64 queries (same results, bounded
+ * scratch).  Logit processors (opadpo_ctx_set_logit_processors) keep their 64-row cap: an armed context with B > 64 is refused, and the refusal disarms. */
 int opadpo_decode_begin(opadpo_ctx* ctx, int adapter_id, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats, int B, int Q,
                         int max_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, int eos_id, int pad_id, int suppress_eos,
                         int32_t* history, void* stream);
@@ -475,7 +489,8 @@ int opadpo_decode_begin(opadpo_ctx* ctx, int adapter_id, const int32_t* ids, con
  * with the generation's temperature / top_k / top_p; scores_raw != 0: the biased logits themselves (greedy decoding, which the host asks for
  * as top_k = 1).  opadpo_decode_begin reads the setting and opadpo_decode_end clears it: the generation after that runs without either unless
  * this is called again.  n = m = 0 clears it; a generation without it issues exactly the launches it issued before this entry point existed.
- * opadpo_decode_beam_begin refuses an armed context. */
+ * opadpo_decode_beam_begin refuses an armed context, and so does opadpo_decode_begin with B > 64 (opadpo_logit_bias_add / opadpo_gather_scores take at most
+ * 64 rows); either refusal clears the setting. */
 int opadpo_ctx_set_logit_processors(opadpo_ctx* ctx, const int32_t* bias_ids, const float* bias, int n, const int32_t* score_ids, int m,
                                     float* scores, int scores_raw);
 /* one more token for every row: all launches of a step, asynchronous */

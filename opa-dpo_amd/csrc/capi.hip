@@ -184,6 +184,34 @@ int opadpo_gemm_nt_decode(const uint16_t* A, int lda, const uint16_t* B, int ldb
   a.a2_group_n = 0; a.a2_group_stride = 0; a.a1_group_n = 0; a.a1_group_stride = 0; a.alpha = 1.f; a.act = 0; a.out_f32 = mode == 1; a.r_f32 = 0;
   return done(launch_gemm_nt_dec64(a, mode, splits, g_flags, S(stream)), "opadpo_gemm_nt_decode");
 }
+// shared by the two decode entry points: the checks after the M range, then the argument block
+static int decode_gemm_args(GemmNTArgs& a, const char* fn, const uint16_t* A, int lda, const uint16_t* B, int ldb, int K, void* C, int ldc, int mode, int M, int N) {
+  if (N <= 0 || N % 128 || K <= 0 || K % 64) return bad(fn, "N must be a multiple of 128, K of 64");
+  if (!A || !B || !C || lda % 8 || ldb % 8 || ldc % 4 || mode < 0 || mode > 2) return bad(fn, "null operand, misaligned leading dimension or bad mode");
+  a.A1 = A; a.B1 = B; a.A2 = nullptr; a.B2 = nullptr; a.C = C; a.R = nullptr; a.bias = nullptr;
+  a.M = M; a.N = N; a.K1 = K; a.K2 = 0; a.lda1 = lda; a.ldb1 = ldb; a.lda2 = 0; a.ldb2 = 0; a.ldc = ldc; a.ldr = 0;
+  a.a2_group_n = 0; a.a2_group_stride = 0; a.a1_group_n = 0; a.a1_group_stride = 0; a.alpha = 1.f; a.act = 0; a.out_f32 = mode == 1; a.r_f32 = 0;
+  return 0;
+}
+int opadpo_gemm_nt_decode_wide(const uint16_t* A, int lda, const uint16_t* B, int ldb, int K, void* C, int ldc, int mode, int M, int N, int splits,
+                               void* stream) {
+  const char* fn = "opadpo_gemm_nt_decode_wide";
+  if (M < 65 || M > 256) return bad(fn, "M must be 65..256 (opadpo_gemm_nt_decode takes 0..64)");
+  GemmNTArgs a;
+  const int rc = decode_gemm_args(a, fn, A, lda, B, ldb, K, C, ldc, mode, M, N);
+  return rc ? rc : done(launch_gemm_nt_decw(a, mode, splits, g_flags, S(stream)), fn);
+}
+// test entry point (not in the public header): the launch opadpo_gemm_nt_decode (M <= 64) / opadpo_gemm_nt_decode_wide (M >= 65) would make under
+// process word use_tr, as one `kernel grid.x grid.y block LDS` line; the same validation, nothing is launched, the operand pointers are never read
+int opadpo_debug_gemm_nt_decode_plan(int M, int N, int K, int mode, int splits, int use_tr, char* out, int out_len) {
+  const char* fn = "opadpo_debug_gemm_nt_decode_plan";
+  if (M < 1 || M > 256) return bad(fn, "M must be 1..256");
+  if (!out || out_len <= 0) return bad(fn, "output buffer");
+  GemmNTArgs a;
+  static const uint16_t dummy[8] = {};
+  const int rc = decode_gemm_args(a, fn, dummy, K, dummy, K, K, (void*)dummy, mode == 2 ? N / 2 : N, mode, M, N);
+  return rc ? rc : done(gemm_nt_decode_plan_text(a, mode, splits, kernel_flags(10, use_tr), out, (size_t)out_len), fn);
+}
 int opadpo_gemm_nt_decode_splits(int N, int K, int splits) { return (N > 0 && K >= 64) ? gemm_nt_dec64_splits(N, K, splits, g_flags) : 1; }
 int opadpo_rmsnorm_sum_fwd(const void* resid, int resid_f32, const float* partials, int n_partials, size_t partial_stride, const uint16_t* w,
                            float* x_out, uint16_t* y, float* rstd, int rows, int H, float eps, void* stream) {

@@ -302,7 +302,7 @@ struct opadpo_ctx {
     bf16_t *kc, *vc; uint8_t* key_mask; float *x, *x2, *hs; bf16_t *hn, *emb;
     LayerBufs b;                    // the one layer slot of a step's B rows: h = post-attention residual stream, rstd1 = rstd2 = rstd, no lse
     float *rstd, *logits; int32_t *cur_tok, *step_d, *pos_d; uint8_t* finished; void* ws; size_t ws_bytes;
-    float *part_o, *part_d; int split_o = 1, split_d = 1; bool use64 = false;      // K-split partial tiles of the 9..64-token decode GEMMs
+    float *part_o, *part_d; int split_o = 1, split_d = 1; bool use64 = false;      // K-split partial tiles of the 9..256-token decode GEMMs
     int32_t* history; float temperature; int top_k; float top_p; uint64_t seed; int eos_id, pad_id, suppress_eos;
     // logit bias of every step and the step-0 scores (opadpo_ctx_set_logit_processors): `logit` = the host copy this generation took, the device tables
     // live in the arena (carved only when armed)
@@ -1358,6 +1358,10 @@ int opadpo_seq_logprobs_bwd(opadpo_ctx* c, opadpo_saved* sv, const float* dlogp,
 }
 
 // ---- rollout: prefill + KV-cache decode (generate.py; online_generator.py:292-309) ----------------------------------------------
+// the decode GEMM of the use64 layer shape: the <= 64-token kernel, or the 65..256-token one (same modes, same K-split, same sums per row)
+static hipError_t decode_gemm(opadpo_ctx* c, const GemmNTArgs& g, int mode, int splits, hipStream_t st) {
+  return g.M > 64 ? launch_gemm_nt_decw(g, mode, splits, ctx_flags(c), st) : launch_gemm_nt_dec64(g, mode, splits, ctx_flags(c), st);
+}
 // rows = D.B, or the items of a beam decode for its step 0 (the prefill's last rows; every beam of an item reads the item's logits row)
 static hipError_t decode_head(opadpo_ctx* c, const float* src_f32, const float* partials, int n_partials, hipStream_t st, int rows = -1) {
   opadpo_ctx::Decode& D = c->dec;
@@ -1366,7 +1370,7 @@ static hipError_t decode_head(opadpo_ctx* c, const float* src_f32, const float* 
   if (n_partials > 0) TRY(launch_rmsnorm_sum_fwd(src_f32, 1, partials, n_partials, (size_t)D.B * d.hidden, c->norm, D.x2, D.hn, D.rstd, rows, d.hidden, d.rms_eps, st));
   else TRY(launch_rmsnorm_fwd(src_f32, 1, c->norm, D.hn, D.rstd, rows, d.hidden, d.rms_eps, st));
   GemmNTArgs g = gemm(D.hn, d.hidden, c->lm_head, d.hidden, d.hidden, D.logits, d.vocab, 1, rows, d.vocab); g.act |= OPADPO_GEMM_STREAM;
-  TRY(D.use64 && rows == D.B ? launch_gemm_nt_dec64(g, 1, 1, ctx_flags(c), st) : run_gemm(c, g, st));
+  TRY(D.use64 && rows == D.B ? decode_gemm(c, g, 1, 1, st) : run_gemm(c, g, st));
   if (D.beams) {
     TRY(launch_beam_step(D.logits, d.vocab, rows == D.B ? 1 : D.beams, D.items, D.beams, d.vocab, D.max_new, D.eos_id, D.pad_id, D.step_d, 0, D.bs, st));
     hipLaunchKernelGGL(add_i32_kernel, dim3(1), dim3(64), 0, st, D.step_d, 1);
@@ -1407,13 +1411,13 @@ static hipError_t decode_one(opadpo_ctx* c, hipStream_t st) {
   TRY(hipGetLastError());
   TRY(launch_gather_rows(c->embed, H, D.cur_tok, D.emb, B, H, st));
   if (D.use64) {
-    // 9..64 tokens: the decode GEMMs for <= 64 tokens (opadpo_gemm_nt_decode); x / b.h = fp32 residual stream, part_o / part_d = K-slice partial tiles of the o / down
+    // 9..256 tokens: the decode GEMMs (opadpo_gemm_nt_decode up to 64 tokens, opadpo_gemm_nt_decode_wide above); x / b.h = fp32 residual stream, part_o / part_d = K-slice partial tiles of the o / down
     // projections, added (in slice order) by the RMSNorm that follows them
     const int F = d.ffn;
     const size_t pstride = (size_t)B * H;
     auto dg = [&](const bf16_t* A, int lda, const bf16_t* W, int K, void* C, int ldc, int N, int mode, int splits) {
       GemmNTArgs g = gemm(A, lda, W, K, K, C, ldc, mode == 1, B, N);
-      return launch_gemm_nt_dec64(g, mode, splits, ctx_flags(c), st);
+      return decode_gemm(c, g, mode, splits, st);
     };
     for (int i = 0; i < d.n_layers; ++i) {
       const opadpo_layer_weights& w0 = c->layers[i];
@@ -1461,7 +1465,10 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
   const opadpo_ctx::Adapter& ad = c->adapters[adapter_id];
   const int side = d.image_size / d.patch, P = side * side, H = d.hidden, F = d.ffn, r = d.lora_r, nh = d.n_heads, hd = d.head_dim, V = d.vocab;
   const int B = beams ? items * beams : items;           // decode rows
-  const int Lp = Q + P - 1, max_ctx = Lp + max_new_tokens, M = items * Lp;
+  // the prefill of more than 64 queries runs in passes of 64: its scratch (and the 32-bit offsets of its GEMMs) stay those of a 64-query rollout,
+  // and every kernel of it computes a row independently of how many rows share the launch - the results are those of one pass
+  const int pf_items = std::min(items, 64);
+  const int Lp = Q + P - 1, max_ctx = Lp + max_new_tokens, M = pf_items * Lp;
   const int kv_len = beams ? Lp : max_ctx;                // cache slots per prefill sequence
   CK(ensure_rope(c, max_ctx, st));
   opadpo_ctx::Decode& D = c->dec;
@@ -1473,7 +1480,9 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
   // 9..64 sequences without LoRA tails (adapter-free or merged adapter): the decode GEMM for <= 64 tokens (gemm_nt_dec64x_kernel), the o / down
   // projections K-split into fp32 partial tiles that the following RMSNorm adds.  Measured per decode step against the 8/16-row streaming kernels
   // of the other path: B = 16 4.84 vs 5.15 ms, B = 8 4.12 vs 3.80 ms.  Context flag bit 5 keeps those.
-  D.use64 = B >= 9 && B <= 64 && ad.kind != 1 && H <= 256 * 8 * 3 && F % 64 == 0 && !c->streaming_dec_gemm;
+  // 65..256 sequences: the same layer shape on the 65..256-token kernel (gemm_nt_decw_kernel).  With an unmerged adapter (kind 1) such a batch takes the
+  // other path, whose projections + LoRA tails run on the tiled gemm_nt kernels above 64 rows: correct, not optimised (include/opadpo_hip.h).
+  D.use64 = B >= 9 && B <= 256 && ad.kind != 1 && H <= 256 * 8 * 3 && F % 64 == 0 && !c->streaming_dec_gemm;
   D.split_o = D.use64 ? gemm_nt_dec64_splits(H, H, 0, ctx_flags(c)) : 1;
   D.split_d = D.use64 ? gemm_nt_dec64_splits(H, F, 0, ctx_flags(c)) : 1;
   auto layout = [&](void* base) {
@@ -1510,14 +1519,14 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
   D.active = true;
   // ---- prefill through the full-sequence kernels (scratch arena released afterwards) ----
   opadpo_saved pf;
-  pf.S = items; pf.L = Lp; pf.T = 1; pf.K = 1; pf.M = M; pf.R = items; pf.train = 0; pf.nb = 1;
+  pf.S = pf_items; pf.L = Lp; pf.T = 1; pf.K = 1; pf.M = M; pf.R = pf_items; pf.train = 0; pf.nb = 1;
   size_t pbytes = 0;
   auto playout = [&](void* base) {
     Carve cv(base);
     pf.x = cv.take<float>(3 * (size_t)M * H);
-    pf.lb = carve_layer_bufs(cv, d, 1, M, items, Lp);
-    pf.key_mask = cv.take<uint8_t>((size_t)items * Lp); pf.rows = cv.take<int32_t>(items);
-    pf.labels = cv.take<int32_t>(items);          // reused as feat_row = arange(items): every prompt carries its own image
+    pf.lb = carve_layer_bufs(cv, d, 1, M, pf_items, Lp);
+    pf.key_mask = cv.take<uint8_t>((size_t)pf_items * Lp); pf.rows = cv.take<int32_t>(pf_items);
+    pf.labels = cv.take<int32_t>(pf_items);       // reused as feat_row = arange(items of a pass): every prompt carries its own image
     return cv.off;
   };
   pbytes = playout(nullptr);
@@ -1529,32 +1538,38 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
     hipError_t e_ = (expr);                                                                               \
     if (e_ != hipSuccess) { ctx_free(c, parena, pbytes); opadpo_decode_end(c); return cfail(c, e_, fn); } \
   } while (0)
-  hipLaunchKernelGGL(affine_index_kernel, g1(items), dim3(256), 0, st, pf.labels, items, 1, 0);       // feat_row = arange(items)
-  CKD(hipGetLastError());
-  CKD(launch_embed_splice(ids, text_mask, c->embed, feats, pf.labels, nullptr, pf.x, 1, pf.key_mask, items, Q, P, H, OPADPO_IMAGE_TOKEN, st));
-  if (beams) CKD(hipMemcpyAsync(D.key_mask, pf.key_mask, (size_t)items * Lp, hipMemcpyDeviceToDevice, st));    // the prefix mask; suffix keys are all visible
-  else {
-    hipLaunchKernelGGL(decode_mask_kernel, g1((size_t)B * max_ctx), dim3(256), 0, st, pf.key_mask, D.key_mask, B, Lp, max_ctx);
-    CKD(hipGetLastError());
-  }
   const size_t MH = (size_t)M * H, per_layer = (size_t)items * nh * kv_len * hd;
   const LayerBufs pb = slot(d, &pf, 0);
   float* const Yp = pf.x + 2 * MH;
-  const float* yin = nullptr;
   const bool fr = !c->resid_deferred;              // residual adds in the projections' epilogues: a layer writes its output into the other x slot
-  const float* xin = pf.x;
-  for (int i = 0; i < d.n_layers; ++i) {
-    float* const xo = fr ? pf.x + (size_t)((i + 1) & 1) * MH : Yp;
-    CKD(layer_fwd(c, i, ad, fr ? xin : (i == 0 ? pf.x : pb.h), yin, pf.x + (size_t)(i & 1) * MH, xo, pb, items, Lp, pf.key_mask, 0, 0, D.kc + i * per_layer,
-                  D.vc + i * per_layer, kv_len, st));
-    if (fr) xin = xo; else yin = Yp;
-  }
-  hipLaunchKernelGGL(affine_index_kernel, g1(items), dim3(256), 0, st, pf.rows, items, Lp, Lp - 1);
-  CKD(hipGetLastError());
-  if (fr) CKD(launch_gather_rows((const bf16_t*)xin, 2 * H, pf.rows, (bf16_t*)D.hs, items, 2 * H, st));   // last position of the last layer's output
-  else {
-    CKD(launch_gather_rows((const bf16_t*)pb.h, 2 * H, pf.rows, (bf16_t*)D.hs, items, 2 * H, st));        // last position: x = h + y, added by the head's norm
-    CKD(launch_gather_rows((const bf16_t*)Yp, 2 * H, pf.rows, (bf16_t*)D.x, items, 2 * H, st));
+  for (int s0 = 0; s0 < items; s0 += pf_items) {   // one pass per pf_items queries (one pass up to 64 queries)
+    const int n = std::min(pf_items, items - s0);
+    const size_t kv0 = (size_t)s0 * nh * kv_len * hd;      // the pass's first sequence inside a layer's cache
+    hipLaunchKernelGGL(affine_index_kernel, g1(n), dim3(256), 0, st, pf.labels, n, 1, 0);       // feat_row = arange(n)
+    CKD(hipGetLastError());
+    CKD(launch_embed_splice(ids + (size_t)s0 * Q, text_mask + (size_t)s0 * Q, c->embed, feats + (size_t)s0 * P * H, pf.labels, nullptr, pf.x, 1, pf.key_mask, n, Q, P, H,
+                            OPADPO_IMAGE_TOKEN, st));
+    if (beams) CKD(hipMemcpyAsync(D.key_mask, pf.key_mask, (size_t)items * Lp, hipMemcpyDeviceToDevice, st));    // the prefix mask; suffix keys are all visible (B * k <= 64: one pass)
+    else {
+      hipLaunchKernelGGL(decode_mask_kernel, g1((size_t)n * max_ctx), dim3(256), 0, st, pf.key_mask, D.key_mask + (size_t)s0 * max_ctx, n, Lp, max_ctx);
+      CKD(hipGetLastError());
+    }
+    const float* yin = nullptr;
+    const float* xin = pf.x;
+    for (int i = 0; i < d.n_layers; ++i) {
+      float* const xo = fr ? pf.x + (size_t)((i + 1) & 1) * MH : Yp;
+      CKD(layer_fwd(c, i, ad, fr ? xin : (i == 0 ? pf.x : pb.h), yin, pf.x + (size_t)(i & 1) * MH, xo, pb, n, Lp, pf.key_mask, 0, 0, D.kc + i * per_layer + kv0,
+                    D.vc + i * per_layer + kv0, kv_len, st));
+      if (fr) xin = xo; else yin = Yp;
+    }
+    hipLaunchKernelGGL(affine_index_kernel, g1(n), dim3(256), 0, st, pf.rows, n, Lp, Lp - 1);
+    CKD(hipGetLastError());
+    float* const hs = D.hs + (size_t)s0 * H;
+    if (fr) CKD(launch_gather_rows((const bf16_t*)xin, 2 * H, pf.rows, (bf16_t*)hs, n, 2 * H, st));   // last position of the last layer's output
+    else {
+      CKD(launch_gather_rows((const bf16_t*)pb.h, 2 * H, pf.rows, (bf16_t*)hs, n, 2 * H, st));        // last position: x = h + y, added by the head's norm
+      CKD(launch_gather_rows((const bf16_t*)Yp, 2 * H, pf.rows, (bf16_t*)(D.x + (size_t)s0 * H), n, 2 * H, st));
+    }
   }
   CKD(hipMemsetAsync(D.finished, 0, beams ? items : B, st));
   CKD(hipMemsetAsync(D.step_d, 0, sizeof(int32_t), st));
@@ -1594,10 +1609,12 @@ int opadpo_decode_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const
   // the setting is for THIS call, accepted or refused; opadpo_decode_end (below, and at the end of the generation) clears what is left of it
   opadpo_ctx::LogitArm arm = std::move(c->next_logit);
   c->next_logit = {};
+  if (B > 256) return cbad(c, __func__, "decode batch above 256 per device is not supported by the decode GEMMs (opadpo_gemm_nt_decode_wide: M <= 256)");
+  if (B > 64 && (!arm.bias_ids.empty() || !arm.score_ids.empty()))      // the setting is consumed by the refusal, as by the beam entry point's
+    return cbad(c, __func__, "logit bias / first-token scores (opadpo_ctx_set_logit_processors) take at most 64 rows: decode batch above 64 is not supported with them");
   if (!weights_ready(c)) return cbad(c, __func__, "LLM weights not set");
   if (adapter_id < 0 || adapter_id >= OPADPO_MAX_ADAPTERS) return cbad(c, __func__, "adapter id out of range");
   if (!ids || !text_mask || !feats || !history || B <= 0 || Q <= 0 || max_new_tokens <= 0 || temperature <= 0.f) return cbad(c, __func__, "null operand or bad shape");
-  if (B > 64) return cbad(c, __func__, "decode batch above 64 per device is not supported by the weight-streaming GEMMs");
   opadpo_decode_end(c);
   c->dec.logit = std::move(arm);
   return decode_begin_impl(c, __func__, adapter_id, ids, text_mask, feats, B, Q, 0, max_new_tokens, temperature, top_k, top_p, seed, eos_id, pad_id,

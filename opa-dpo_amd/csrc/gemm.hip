@@ -2595,6 +2595,192 @@ __global__ __launch_bounds__(64 * (NW + 2), NW == 8 ? 1 : 2) void gemm_nt_dec64x
     }
   }
 }
+// ---------------------------------------------------------------------------------------------------
+// gemm_nt "decw" kernel: the decode GEMM for 65..256 tokens (rollout at 65..256 sequences per device; opadpo_gemm_nt_decode_wide).
+// The dec64x kernel above with the token rows walked in GROUPS: a workgroup still owns 16 * NW weight rows x one K range and streams them
+// global -> registers in whole 128-byte lines (same loads, same lane shuffle, four k-tiles = 8 loads in flight per wave), so every weight
+// row leaves HBM exactly once per launch whatever M is; the MFMA operand built from a k-tile's weights is then used against G = ceil(M / 64)
+// groups of 64 token rows (4 fragments each) before its registers are reloaded.  The activations of all 64 * G rows are staged through LDS by
+// the two loader waves in HALF chunks of two k-tiles (128 deep: 64 * G rows x 256 B = 32 KiB * G per stage, two stages, 16-byte pieces XOR-ed
+// with token & 15 as above), one barrier per half chunk.  LDS fragment reads of the next (k-tile, group) are requested before the MFMAs of
+// the current one (two register images of one group).
+// Per output element the sum runs over the k-tiles of its K slice in order, two MFMAs per k-tile - the order of the dec64x kernel, fixed by
+// (N, K, splits) alone: a row's result does not depend on M, on the rows per workgroup, or on which of the two kernels computed it.
+// What bounds it is the same vector-memory budget per CU (weights + activation pieces): the activation bytes per weight byte are M / (16 * NW),
+// so the rows per workgroup are chosen by the cost estimate of plan_gemm_nt_dec64 with the wider token count.
+// ---------------------------------------------------------------------------------------------------
+constexpr int W_HK = 2;                                  // k-tiles (64 deep) per activation half chunk
+constexpr int W_ROWB = W_HK * D_BK * 2;                  // bytes per token row and stage (256)
+constexpr int W_STAGE64 = 64 * W_ROWB;                   // stage bytes per group of 64 token rows (16 KiB)
+template <int G, int MODE, int NW>      // G = groups of 64 token rows (2..4); NW = weight waves (16 rows each): 3, 4, 6 (SwiGLU pairs) or 8; two more waves load the activations
+__global__ __launch_bounds__(64 * (NW + 2), 1) void gemm_nt_decw_kernel(GemmNTArgs p) {
+  static_assert(G >= 2 && G <= 4, "65..256 token rows");
+  static_assert(NW == 3 || NW == 4 || NW == 6 || NW == 8, "48, 64, 96 or 128 weight rows per workgroup");
+  static_assert(MODE != 2 || NW != 3, "SwiGLU pairs: 32 + 32, 48 + 48 or 64 + 64 rows");
+  static_assert(MODE == 2 || NW != 6, "96-row workgroups: SwiGLU pairs only");
+  constexpr int MF = 4 * G, STAGE = G * W_STAGE64;
+  extern __shared__ __attribute__((aligned(16))) char smem[];          // 2 activation stages
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int bt = blockIdx.x, split = blockIdx.y, splits = gridDim.y;
+  const int nt = p.K1 / D_BK;
+  const int per = (nt + splits - 1) / splits;
+  const int t0 = split * per, t1 = min(nt, t0 + per);
+  const int nk = max(t1 - t0, 0), nh = (nk + W_HK - 1) / W_HK;
+  // weight rows of the workgroup and of a wave: as in gemm_nt_dec64x_kernel (MODE 2: half gate rows, half up rows; the waves of a partly filled
+  // last workgroup redo its last 16 valid rows and store nothing)
+  constexpr int ROWS = 16 * NW, HALF = ROWS / 2;
+  const int n0 = MODE == 2 ? 0 : bt * ROWS;
+  const int gw = wave < NW ? (wave < NW / 2 ? wave : wave - NW / 2) : 0;
+  const int g_raw = bt * HALF + gw * 16;
+  const bool g_live = MODE != 2 || g_raw < p.N / 2;
+  const int g0 = MODE == 2 ? (g_live ? g_raw : p.N / 2 - 16) : 0;
+  auto wrow = [&](int r) {
+    if (MODE != 2) return n0 + r;
+    const int g = g0 + (r & 15);
+    return (g / 64) * 128 + g % 64 + (r >= HALF ? 64 : 0);
+  };
+  auto uni = [](const void* q) -> void* {
+    const unsigned long long v = (unsigned long long)q;
+    return (void*)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+                   (unsigned)__builtin_amdgcn_readfirstlane((int)v));
+  };
+  const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(uni(p.B1), 0, (int)(((unsigned)(p.N - 1) * (unsigned)p.ldb1 + (unsigned)p.K1) * 2u), 0x00020000);
+  // the last half chunk of a K range may reach past the end of the rows: the descriptor ends with the last row, the overshoot reads zeros
+  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(uni(p.A1), 0, (int)(((unsigned)(p.M - 1) * (unsigned)p.lda1 + (unsigned)p.K1) * 2u), 0x00020000);
+  const int fr = lane & 15, fc = lane >> 4, hi = (lane >> 3) & 1;
+  const unsigned voffWa = (unsigned)wrow(wave * 16 + (lane & 7)) * (unsigned)p.ldb1 * 2u + (unsigned)(fc + 4 * hi) * 16u;
+  const unsigned voffWb = (unsigned)wrow(wave * 16 + 8 + (lane & 7)) * (unsigned)p.ldb1 * 2u + (unsigned)(fc + 4 * (hi ^ 1)) * 16u;
+  // activation pieces: 1 KiB = 4 token rows x 256 B; the 16 * G pieces of a half chunk are dealt 8 * G to each of the two loader waves
+  constexpr int XP = 8 * G;
+  if (wave >= NW) {
+    const int lw = wave - NW;
+    for (int h = 0; h < nh; ++h) {
+      // stage h & 1 held half chunk h-2: every weight wave left it before it arrived at the barrier that started half chunk h-1
+#pragma unroll
+      for (int i = 0; i < XP; ++i) {
+#if defined(__HIP_DEVICE_COMPILE__)      // (device pass only: see gemm_nt_dec64x_kernel)
+        const int row = (lw * XP + i) * 4 + (lane >> 4);
+        const unsigned voffX = (unsigned)min(row, p.M - 1) * (unsigned)p.lda1 * 2u + (unsigned)(((lane & 15) ^ (row & 15)) * 16);
+        // pieces of token rows >= M are not fetched: their accumulator columns are never stored
+        if ((lw * XP + i) * 4 < p.M) __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, LDS_PTR(void, smem + (h & 1) * STAGE + (lw * XP + i) * 1024), 16, voffX, (t0 + h * W_HK) * (D_BK * 2), 0, 0);
+#endif
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();                                    // barrier h: half chunk h is in LDS for everyone
+    }
+    if constexpr (MODE == 2) { __syncthreads(); __syncthreads(); }      // the epilogue's two barriers
+    return;
+  }
+  u32x4_t wa[2 * W_HK], wb[2 * W_HK];                     // weight slots: the k-tiles of TWO half chunks in flight per wave (8 loads)
+  auto load_w = [&](int slot, int t) {
+    // past the K range: an offset beyond the descriptor's end - the load returns zeros without touching memory
+    const bool in = t < t1;
+    const int k2 = t * (D_BK * 2);
+    wa[slot] = __builtin_amdgcn_raw_buffer_load_b128(rW, in ? voffWa : 0xfffffff0u, in ? k2 : 0, 2);       // aux 2 = nt: streamed once
+    wb[slot] = __builtin_amdgcn_raw_buffer_load_b128(rW, in ? voffWb : 0xfffffff0u, in ? k2 : 0, 2);
+  };
+  f32x4_t acc[MF];
+#pragma unroll
+  for (int f = 0; f < MF; ++f) acc[f] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  bf16x8_t xr[2][4][2];
+  auto xread = [&](int buf, int kt, int g, const char* xs) {     // activation fragments of k-tile kt, token group g of the half chunk at xs
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      const char* xrow = xs + (g * 64 + f * 16 + fr) * W_ROWB;
+      xr[buf][f][0] = *(const bf16x8_t*)(xrow + (((kt * 8 + fc) ^ fr) << 4));
+      xr[buf][f][1] = *(const bf16x8_t*)(xrow + (((kt * 8 + 4 + fc) ^ fr) << 4));
+    }
+  };
+  // one half chunk: slots sb, sb + 1 hold its weights; cnt = 1 or 2 k-tiles of it lie inside the K range.  Each slot is reloaded, two half
+  // chunks on, as soon as its MFMAs are issued.
+  auto half = [&](auto slot_base, int h, int cnt) {
+    constexpr int sb = decltype(slot_base)::value;
+    const char* xs = smem + (h & 1) * STAGE;
+    xread(0, 0, 0, xs);
+#pragma unroll
+    for (int kt = 0; kt < W_HK; ++kt) {
+      if (kt < cnt) {
+        u32x4_t a1, tt, a2;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          a1[e] = hi ? wb[sb + kt][e] : wa[sb + kt][e];
+          tt[e] = hi ? wa[sb + kt][e] : wb[sb + kt][e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a2[e] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)tt[e], 0x128, 0xf, 0xf, true);      // row_ror:8
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const int s = kt * G + g;
+          if (g + 1 < G) xread((s + 1) & 1, kt, g + 1, xs);
+          else if (kt + 1 < cnt) xread((s + 1) & 1, kt + 1, 0, xs);
+#pragma unroll
+          for (int f = 0; f < 4; ++f) acc[g * 4 + f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&a1, xr[s & 1][f][0], acc[g * 4 + f], 0, 0, 0);
+#pragma unroll
+          for (int f = 0; f < 4; ++f) acc[g * 4 + f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&a2, xr[s & 1][f][1], acc[g * 4 + f], 0, 0, 0);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      load_w(sb + kt, t0 + (h + 2) * W_HK + kt);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  if (nh > 0) {
+#pragma unroll
+    for (int j = 0; j < 2 * W_HK; ++j) load_w(j, t0 + j);
+    for (int h = 0; h < nh; h += 2) {
+      __syncthreads();                                    // barrier h: half chunk h has landed; everyone is done reading half chunk h-1
+      half(std::integral_constant<int, 0>{}, h, min(W_HK, nk - h * W_HK));
+      if (h + 1 < nh) {
+        __syncthreads();                                  // barrier h+1
+        half(std::integral_constant<int, W_HK>{}, h + 1, min(W_HK, nk - (h + 1) * W_HK));
+      }
+    }
+  }
+  // lane holds C[token f*16 + fr][4 consecutive columns fc*4 .. +3 of the wave's 16 weight rows]
+  if constexpr (MODE == 2) {
+    __syncthreads();                                           // the stages are dead: reuse them for the gate / up exchange
+    float* ex = (float*)smem;                                  // [NW/2 up waves][MF][64 lanes][4]: at most 64 KiB of the 2 * STAGE
+    if (wave >= NW / 2) {
+#pragma unroll
+      for (int f = 0; f < MF; ++f) *(f32x4_t*)(ex + (((wave - NW / 2) * MF + f) * 64 + lane) * 4) = acc[f];
+    }
+    __syncthreads();
+    if (wave < NW / 2) {
+#pragma unroll
+      for (int f = 0; f < MF; ++f) {
+        const int m = f * 16 + fr;
+        if (m >= p.M) continue;
+        const f32x4_t u = *(const f32x4_t*)(ex + ((wave * MF + f) * 64 + lane) * 4);
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float gt = bf2f(f2bf(acc[f][e])), up = bf2f(f2bf(u[e]));
+          o[e] = gt / (1.0f + __expf(-gt)) * up;
+        }
+        uint2 stv;
+        stv.x = pack_bf2(o[0], o[1]);
+        stv.y = pack_bf2(o[2], o[3]);
+        if (g_live) *(uint2*)((bf16_t*)p.C + (size_t)m * p.ldc + g0 + fc * 4) = stv;
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int f = 0; f < MF; ++f) {
+    const int m = f * 16 + fr;
+    if (m >= p.M) continue;
+    const int n = n0 + wave * 16 + fc * 4;
+    if constexpr (MODE == 1) {
+      *(float4*)((float*)p.C + ((size_t)split * p.M + m) * p.ldc + n) = make_float4(acc[f][0], acc[f][1], acc[f][2], acc[f][3]);
+    } else {
+      uint2 stv;
+      stv.x = pack_bf2(acc[f][0], acc[f][1]);
+      stv.y = pack_bf2(acc[f][2], acc[f][3]);
+      *(uint2*)((bf16_t*)p.C + (size_t)m * p.ldc + n) = stv;
+    }
+  }
+}
 }  // namespace
 
 // ==== gemm_nt dispatch: a pure plan of at most three launches from (arguments, flags, CU count), then one loop that launches it ========
@@ -2610,6 +2796,8 @@ struct GemmKernel { const char* name; const void* fn; int block, lds, sig; };
                       GK(64 * (NW + 2), 2 * X_STAGE, SIG_NT, gemm_nt_dec64x_kernel<3, MD, NW>), GK(64 * (NW + 2), 2 * X_STAGE, SIG_NT, gemm_nt_dec64x_kernel<4, MD, NW>)
 #define GK_D64(MD, NS, KW) GK(256, NS * D_STAGE, SIG_NT, gemm_nt_dec64_kernel<1, MD, NS, KW>), GK(256, NS * D_STAGE, SIG_NT, gemm_nt_dec64_kernel<2, MD, NS, KW>), \
                            GK(256, NS * D_STAGE, SIG_NT, gemm_nt_dec64_kernel<3, MD, NS, KW>), GK(256, NS * D_STAGE, SIG_NT, gemm_nt_dec64_kernel<4, MD, NS, KW>)
+#define GK_DW(MD, NW) GK(64 * (NW + 2), 4 * W_STAGE64, SIG_NT, gemm_nt_decw_kernel<2, MD, NW>), GK(64 * (NW + 2), 6 * W_STAGE64, SIG_NT, gemm_nt_decw_kernel<3, MD, NW>), \
+                      GK(64 * (NW + 2), 8 * W_STAGE64, SIG_NT, gemm_nt_decw_kernel<4, MD, NW>)
 // positions in the kernel table (below, same order); MF = 16-row fragments of the token rows ((M + 15) / 16), MF8 = 8-row ones
 enum : int {
   K_X128, K_P8, K_TAIL8, K_TAIL4, K_FOLD_REDUCE,
@@ -2619,7 +2807,8 @@ enum : int {
   K_SK8 = K_SK + 12,     // + 4 * form + MF8 - 1; form 0 SwiGLU pair, 1 16 weight rows per workgroup, 2 32 rows (MF8 1 / 2)
   K_DX = K_SK8 + 10,     // + 12 * mode + 4 * slot + MF - 1; slots: 3 / 4 / 8 weight waves (modes 0, 1), 4 / 6 / 8 (mode 2)
   K_D64 = K_DX + 36,     // + MF - 1: 32-row workgroups (mode 0); + 4 + 8 * mode + 4 * deep ring + MF - 1
-  K_COUNT = K_D64 + 28
+  K_DW = K_D64 + 28,     // + 9 * mode + 3 * slot + G - 2 (G = groups of 64 token rows); slots as K_DX
+  K_COUNT = K_DW + 27
 };
 const GemmKernel g_kernels[] = {
   GK(256, 65536, SIG_NT, gemm_nt_kernel_x<64, true, 2>), GK(512, 2 * P_STAGE, SIG_NT, gemm_nt_p8_kernel),
@@ -2636,7 +2825,9 @@ const GemmKernel g_kernels[] = {
   GK_SK8(1, 4, 4, false), GK_SK8(2, 4, 2, false),
   GK_DX(0, 3), GK_DX(0, 4), GK_DX(0, 8), GK_DX(1, 3), GK_DX(1, 4), GK_DX(1, 8), GK_DX(2, 4), GK_DX(2, 6), GK_DX(2, 8),
   GK_D64(0, 4, 2), GK_D64(0, 4, 1), GK_D64(0, 8, 1), GK_D64(1, 4, 1), GK_D64(1, 8, 1), GK_D64(2, 4, 1), GK_D64(2, 8, 1),
+  GK_DW(0, 3), GK_DW(0, 4), GK_DW(0, 8), GK_DW(1, 3), GK_DW(1, 4), GK_DW(1, 8), GK_DW(2, 4), GK_DW(2, 6), GK_DW(2, 8),
 };
+#undef GK_DW
 #undef GK_D64
 #undef GK_DX
 #undef GK_SK8
@@ -2838,6 +3029,25 @@ hipError_t plan_gemm_nt(const GemmNTArgs& a_in, const KernelFlags& f, int cus, v
   return hipSuccess;
 }
 
+// weight waves (16 rows each) per workgroup of the whole-line decode kernels, by shape: bytes per CU = rounds of workgroups over the 256 CUs x
+// (weight rows + token rows) of a workgroup.  two_per_cu: the kernel fits two 64-row workgroups on a CU (dec64x; the 65..256-token kernel's
+// LDS stages leave room for one).
+int dec_rows_choice(int N, int mode, int splits, int mf, bool two_per_cu, const KernelFlags& f) {
+  int nw = 4;
+  long best = -1;
+  for (const int c : {8, 6, 4, 3}) {
+    // 96-row workgroups (48 gate + 48 up rows) exist for the SwiGLU-pair mode only, where the last workgroup may be partly filled
+    if (mode == 2 ? (c == 3 || (c != 6 && N % (16 * c))) : (c == 6 || N % (16 * c))) continue;
+    const long wgs = (mode == 2 ? (long)(N / 2 + 8 * c - 1) / (8 * c) : (long)(N / (16 * c))) * splits;
+    long cost = ((wgs + 255) / 256) * (16 * c + 16 * mf);
+    if (two_per_cu && c == 4 && wgs > 448 && wgs <= 512) cost = cost * 3 / 4;      // two full rounds of 64-row workgroups, two per CU: measured ahead of one round of 128-row ones (lm_head, 500: 46.8 vs 52.9 us at 8 tokens, 49.8 vs 53.6 at 32, 57.5 vs 57.9 at 64)
+    if (best < 0 || cost < best) { best = cost; nw = c; }
+  }
+  const int nw_force = f.dec64x_nw == 1 ? 3 : f.dec64x_nw == 2 ? 4 : f.dec64x_nw == 3 ? 8 : 0;
+  if (nw_force && N % (16 * nw_force) == 0 && !(mode == 2 && nw_force == 3)) nw = nw_force;
+  return nw;
+}
+
 int dec64_splits(int N, int K, int splits, const KernelFlags& f) {
   const int nt = K / D_BK, tiles = N / D_BN;
   if (splits <= 0) {
@@ -2865,24 +3075,38 @@ hipError_t plan_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, const K
     // ~35 GB/s per CU whatever the source: profiles/r04_decode_stream.txt), so the estimate is bytes per CU = rounds of workgroups over the
     // 256 CUs x (weight rows + token rows) of a workgroup: q|k|v (12288 rows) -> 48-row workgroups (256 of them), gate|up -> 128 rows
     // (172), the K-split projections and the head -> 128 rows.
-    int nw = 4;
-    long best = -1;
-    for (const int c : {8, 6, 4, 3}) {
-      // 96-row workgroups (48 gate + 48 up rows) exist for the SwiGLU-pair mode only, where the last workgroup may be partly filled
-      if (mode == 2 ? (c == 3 || (c != 6 && a.N % (16 * c))) : (c == 6 || a.N % (16 * c))) continue;
-      const long wgs = (mode == 2 ? (long)(a.N / 2 + 8 * c - 1) / (8 * c) : (long)(a.N / (16 * c))) * splits;
-      long cost = ((wgs + 255) / 256) * (16 * c + 16 * mf);
-      if (c == 4 && wgs > 448 && wgs <= 512) cost = cost * 3 / 4;      // two full rounds of 64-row workgroups, two per CU: measured ahead of one round of 128-row ones (lm_head, 500: 46.8 vs 52.9 us at 8 tokens, 49.8 vs 53.6 at 32, 57.5 vs 57.9 at 64)
-      if (best < 0 || cost < best) { best = cost; nw = c; }
-    }
-    const int nw_force = f.dec64x_nw == 1 ? 3 : f.dec64x_nw == 2 ? 4 : f.dec64x_nw == 3 ? 8 : 0;
-    if (nw_force && a.N % (16 * nw_force) == 0 && !(mode == 2 && nw_force == 3)) nw = nw_force;
+    const int nw = dec_rows_choice(a.N, mode, splits, mf, true, f);
     const int slot = nw == 8 ? 2 : nw == (mode == 2 ? 4 : 3) ? 0 : 1;      // modes 0, 1: 3 / 4 / 8 weight waves; mode 2: 4 / 6 / 8
     p.add(K_DX + 12 * mode + 4 * slot + mf - 1, dim3(mode == 2 ? (a.N / 2 + 8 * nw - 1) / (8 * nw) : a.N / (16 * nw), splits), a);
     return hipSuccess;
   }
   if (mode == 0 && tiles <= 256) p.add(K_D64 + mf - 1, dim3(2 * tiles), a);      // 32-row workgroups: twice the blocks for a projection that does not fill the chip
   else p.add(K_D64 + 4 + 8 * mode + (tiles * splits <= 256 ? 4 : 0) + mf - 1, dim3(tiles, splits), a);      // at most one workgroup per CU: a deeper ring instead of a second workgroup
+  return hipSuccess;
+}
+
+// the decode GEMM for 65..256 tokens (gemm_nt_decw_kernel): the shape rules, modes and K-split of plan_gemm_nt_dec64 - the split depends on (N, K)
+// alone, so a row's sums are those of the <= 64-token kernel
+hipError_t plan_gemm_nt_decw(const GemmNTArgs& a, int mode, int splits, const KernelFlags& f, GemmPlan& p) {
+  if (a.M <= 64 || a.M > 256 || a.N % 128 || a.K1 % D_BK || a.K1 <= 0 || a.K2 != 0 || a.lda1 % 8 || a.ldb1 % 8 || mode < 0 || mode > 2) return hipErrorInvalidValue;
+  if ((double)a.M * a.lda1 * 2 >= 4.0e9 || (double)a.N * a.ldb1 * 2 >= 4.0e9) return hipErrorInvalidValue;          // 32-bit buffer offsets
+  splits = dec64_splits(a.N, a.K1, mode != 1 ? 1 : splits, f);
+  const int g = (a.M + 63) / 64;
+  const int nw = dec_rows_choice(a.N, mode, splits, (a.M + 15) / 16, false, f);
+  const int slot = nw == 8 ? 2 : nw == (mode == 2 ? 4 : 3) ? 0 : 1;
+  p.add(K_DW + 9 * mode + 3 * slot + g - 2, dim3(mode == 2 ? (a.N / 2 + 8 * nw - 1) / (8 * nw) : a.N / (16 * nw), splits), a);
+  return hipSuccess;
+}
+
+hipError_t plan_text(const GemmPlan& p, char* out, size_t out_len) {
+  size_t used = 0;
+  if (out_len) out[0] = 0;
+  for (int i = 0; i < p.n; ++i) {
+    const GemmKernel& k = g_kernels[p.l[i].kernel];
+    const int w = snprintf(out + used, out_len - used, "%s %u %u %d %d\n", k.name, p.l[i].grid.x, p.l[i].grid.y, k.block, k.lds);
+    if (w < 0 || (size_t)w >= out_len - used) return hipErrorInvalidValue;
+    used += w;
+  }
   return hipSuccess;
 }
 
@@ -2929,16 +3153,17 @@ int gemm_nt_dec64_splits(int N, int K, int splits, const KernelFlags& f) { retur
 hipError_t gemm_nt_plan_text(const GemmNTArgs& a, const KernelFlags& f, int cus, char* out, size_t out_len) {
   GemmPlan p;
   const hipError_t e = plan_gemm_nt(a, f, cus, nullptr, p);
-  if (e != hipSuccess) return e;
-  size_t used = 0;
-  if (out_len) out[0] = 0;
-  for (int i = 0; i < p.n; ++i) {
-    const GemmKernel& k = g_kernels[p.l[i].kernel];
-    const int w = snprintf(out + used, out_len - used, "%s %u %u %d %d\n", k.name, p.l[i].grid.x, p.l[i].grid.y, k.block, k.lds);
-    if (w < 0 || (size_t)w >= out_len - used) return hipErrorInvalidValue;
-    used += w;
-  }
-  return hipSuccess;
+  return e != hipSuccess ? e : plan_text(p, out, out_len);
+}
+hipError_t launch_gemm_nt_decw(const GemmNTArgs& a, int mode, int splits, const KernelFlags& f, hipStream_t st) {
+  GemmPlan p;
+  const hipError_t e = plan_gemm_nt_decw(a, mode, splits, f, p);
+  return e != hipSuccess ? e : launch_plan(p, st);
+}
+hipError_t gemm_nt_decode_plan_text(const GemmNTArgs& a, int mode, int splits, const KernelFlags& f, char* out, size_t out_len) {
+  GemmPlan p;
+  const hipError_t e = a.M > 64 ? plan_gemm_nt_decw(a, mode, splits, f, p) : plan_gemm_nt_dec64(a, mode, splits, f, p);
+  return e != hipSuccess ? e : plan_text(p, out, out_len);
 }
 
 hipError_t launch_gemm_tn_group(const GemmTNArgs* list, int n, const KernelFlags& f, hipStream_t st, void* workspace, size_t workspace_bytes, int* all_ordered) {

@@ -160,6 +160,10 @@ hipError_t launch_rmsnorm_sum_fwd(const void* resid, int resid_f32, const float*
                                   float* x_out, bf16_t* y, float* rstd, int rows, int H, float eps, hipStream_t st);
 hipError_t launch_gemm_nt_dec64(const GemmNTArgs& a, int mode, int splits, const KernelFlags& f, hipStream_t st);
 int gemm_nt_dec64_splits(int N, int K, int splits, const KernelFlags& f);
+// the same product for 65 <= M <= 256 (gemm_nt_decw_kernel): modes, shape rules and K-split (gemm_nt_dec64_splits) as above
+hipError_t launch_gemm_nt_decw(const GemmNTArgs& a, int mode, int splits, const KernelFlags& f, hipStream_t st);
+// the launch either decode entry would make, as text (one `kernel grid.x grid.y block LDS` line); nothing is launched
+hipError_t gemm_nt_decode_plan_text(const GemmNTArgs& a, int mode, int splits, const KernelFlags& f, char* out, size_t out_len);
 hipError_t launch_rmsnorm_bwd(const bf16_t* dy, const void* x, int x_f32, const bf16_t* w, const float* rstd, const void* dres,
                               int dres_f32, float* dx_f32, bf16_t* dx_bf16, int rows, int H, hipStream_t st);
 hipError_t launch_layernorm_fwd(const void* x, const bf16_t* w, const bf16_t* b, void* y, int rows, int H, float eps, hipStream_t st, int x_f32 = 0, int y_f32 = 0);

@@ -31,6 +31,7 @@ SIGNATURES = {
     "opadpo_gemm_nt_rope_pos": [_p, _i, _p, _i, _i, _p, _i, _p, _i, _i, _i, _i, _p, _i, _i, _i, _p, _f, _i, _p],
     "opadpo_gemm_nt_decode": [_p, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p],
     "opadpo_gemm_nt_decode_splits": [_i, _i, _i],
+    "opadpo_gemm_nt_decode_wide": [_p, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p],
     "opadpo_rmsnorm_sum_fwd": [_p, _i, _p, _i, _sz, _p, _p, _p, _p, _i, _i, _f, _p],
     "opadpo_gemm_tn": [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p],
     "opadpo_gemm_tn_group": [_i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _f, _p],
@@ -219,7 +220,8 @@ _stream_weights = False
 
 
 class decode_schedule:
-    """with decode_schedule(): every gemm_nt with M <= 64 takes the weight-streaming kernel (OPADPO_GEMM_STREAM)."""
+    """with decode_schedule(): every gemm_nt with M <= 64 takes the weight-streaming kernel (OPADPO_GEMM_STREAM); a product of more rows
+    (a rollout of 65..256 sequences through the op-level engine) keeps the tiled kernels and is not given the hint."""
 
     def __enter__(self):
         global _stream_weights
@@ -259,7 +261,7 @@ def gemm_nt(a1: torch.Tensor, b1: torch.Tensor, out: torch.Tensor, *, a2: Option
          ptr(a2), a2.stride(0) if a2 is not None else 0, ptr(b2), b2.stride(0) if b2 is not None else 0, K2,
          a2_group_n, a2_group_stride, a1_group_n, a1_group_stride, ptr(out), out.stride(0), int(out_f32),
          ptr(residual), residual.stride(0) if residual is not None else 0, int(res_f32), ptr(bias), M, N, float(alpha),
-         act | (GEMM_STREAM if _stream_weights else 0), stream())
+         act | (GEMM_STREAM if _stream_weights and M <= 64 else 0), stream())
     if PROFILE is not None:
         e1.record()
         PROFILE.append((2.0 * M * N * (K1 + K2), e0, e1))

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Rollout (config 5 of BASELINE.json) micro-benchmark on one MI355X: LLaVA-1.5-7B prefill (Q=128 -> L=703) + KV-cache
 sampling decode (top-k 30, top-p 0.95), random-init weights, no LoRA (the shipped rollout config; RB_LORA=1 / 2 adds a frozen
-adapter unmerged / merged, RB_FUSE=0 switches the fused SwiGLU gate|up projection off, RB_BATCH = sequences per device, shipped: 4).
-Reports prefill ms, decode ms/step and tokens/s; the decode roofline is HBM: >= 13.2 GB of bf16 weights per step."""
+adapter unmerged / merged, RB_FUSE=0 switches the fused SwiGLU gate|up projection off, RB_BATCH = sequences per device, 1..256, shipped: 4;
+RB_STEPS = new tokens, 896 is the recipe's response length, 64 the short evaluation's).
+Reports prefill ms, decode ms/step and tokens/s; the decode roofline is HBM: >= 13.2 GB of bf16 weights per step plus the KV cache the step reads
+(0.5 MB per cached token at 7B: it dominates from about 40 sequences at the recipe's context)."""
 import json
 import os
 import sys
@@ -51,9 +53,11 @@ def main():
     prefill = res[1]
     per_step = (res[steps] - res[1]) / (steps - 1)
     wbytes = 2 * (d.n_layers * (4 * d.hidden ** 2 + 3 * d.hidden * d.ffn) + d.vocab * d.hidden)
-    out = {"model": model, "batch": B, "adapter": ["none", "lora", "lora merged"][lora], "fused_swiglu": gen.adapter is not None and getattr(gen.adapter, "merged", None) is not None, "prefill_ms": prefill * 1e3, "decode_ms_per_step": per_step * 1e3,
+    # K and V of every cached token are read once per step: the mean context over the timed steps is the prefill length + half the new tokens
+    kv_bytes = 2 * 2 * d.n_layers * d.hidden * B * (Q + d.n_patches - 1 + steps / 2)
+    out = {"model": model, "batch": B, "new_tokens": steps, "adapter": ["none", "lora", "lora merged"][lora], "fused_swiglu": gen.adapter is not None and getattr(gen.adapter, "merged", None) is not None, "prefill_ms": prefill * 1e3, "decode_ms_per_step": per_step * 1e3,
            "decode_tokens_per_s": B / per_step, "weight_bytes_per_step_GB": wbytes / 1e9,
-           "decode_hbm_frac": wbytes / per_step / 8e12}
+           "decode_hbm_frac": wbytes / per_step / 8e12, "kv_bytes_per_step_GB": kv_bytes / 1e9, "decode_bytes_over_8TBs_ms": (wbytes + kv_bytes) / 8e12 * 1e3}
     print(json.dumps(out))
     os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
     json.dump(out, open(os.path.join(REPO, "gpurun_out", f"rollout_bench_b{B}_l{lora}.json"), "w"))
