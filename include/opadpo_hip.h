@@ -313,6 +313,24 @@ int opadpo_attn_decode_beam(const uint16_t* qkv, int ld, const float* cos_tab, c
                             const uint16_t* v_prefix, uint16_t* k_suffix, uint16_t* v_suffix, uint16_t* o, const uint8_t* prefix_mask, int B, int k,
                             int nh, int hd, const int32_t* pos_ptr, int Lp, int max_new, const int32_t* table, float scale, void* workspace,
                             size_t workspace_bytes, void* stream);
+/* n sampled responses per prompt (HF generate(do_sample=True, num_return_sequences=n)): inputs expand as repeat_interleave(n), row b is sample
+ * b % n of item b / n; 1 <= n <= OPADPO_MAX_RETURN_SEQUENCES.  Decode attention of such rows: the items' prefix caches [items, nh, Lp, hd]
+ * (prefix_mask [items, Lp], nullable) are stored once and shared by the item's n rows; suffix caches [items*n, nh, max_new, hd] per row.  Each call
+ * rotates q and the new k at pos_ptr[0] (>= Lp), appends k and v at suffix slot pos - Lp of row b, and attends the item's unmasked prefix keys plus
+ * suffix slots 0 .. pos - Lp of its own row.  form: 1 = per-row (the beam kernel with the identity slot table: output and appended K/V bit-identical
+ * to opadpo_attn_decode_fused on the materialised per-row cache), 2 = grouped (head_dim 128 only, refused otherwise: one workgroup per (item, head,
+ * prefix key range) reads every K/V tile once for the item's n rows on v_mfma_f32_16x16x32_bf16; the softmax weights are rounded to bf16 for the
+ * P.V product - the one rounding point it adds; the suffix keys go through the per-row kernel and a merge launch combines the partials; appended
+ * K/V bit-identical to form 1), 0 = the library's choice (grouped for n >= 2 at head_dim 128).  Prefix key ranges of the grouped form:
+ * R = min(max(1, 256 / (items*nh)), max(1, Lp / 64)), range stride per = ceil(ceil(Lp / R) / 64) * 64 keys, ranges = ceil(Lp / per), the last one
+ * holding the remainder.
+ * workspace: at least opadpo_attn_decode_shared_workspace_bytes(...) bytes (enough for either form), refused below that. */
+#define OPADPO_MAX_RETURN_SEQUENCES 16
+size_t opadpo_attn_decode_shared_workspace_bytes(int items, int n, int nh, int hd, int Lp, int max_new);
+int opadpo_attn_decode_shared(const uint16_t* qkv, int ld, const float* cos_tab, const float* sin_tab, const uint16_t* k_prefix,
+                              const uint16_t* v_prefix, uint16_t* k_suffix, uint16_t* v_suffix, uint16_t* o, const uint8_t* prefix_mask, int items,
+                              int n, int nh, int hd, const int32_t* pos_ptr, int Lp, int max_new, float scale, void* workspace,
+                              size_t workspace_bytes, int form, void* stream);
 /* One beam-search step at step index `step` (0 = the first generated token: only beam 0 of an item is live) on fp32 logits [B*k, V] (ldl
  * apart).  Candidates are ranked by log_softmax + beam score, ties to the lower flat index beam*V + token.  Caller-owned device state, all
  * zero-initialised before step 0 except as noted:
@@ -404,7 +422,9 @@ int opadpo_ctx_set_allocator(opadpo_ctx* ctx, opadpo_alloc_fn alloc, opadpo_free
  *   keep their bits; -1.0 % per step.
  * bit 14 = SwiGLU backward as its own kernel (silu_mul_bwd; rounds 1-4).  Default since round 5: inside the direct epilogue of the down projection's
  *   dgrad (OPADPO_ACT_SWIGLU_BWD, gate / up operands requested one row block ahead; bit-identical to the two-kernel form, d_act never reaches HBM;
- *   -0.8 % per step); bit 6 selects the LDS-staged form of that epilogue (rounds 3-4; cross-check). */
+ *   -0.8 % per step); bit 6 selects the LDS-staged form of that epilogue (rounds 3-4; cross-check).
+ * bit 15 = the shared-prefix decode attention of opadpo_decode_begin_n stays per-row (opadpo_attn_decode_shared form 1: the tokens of the
+ *   repeated-prompt rollout; cross-check).  Default: the library's choice (grouped for n >= 2 at head_dim 128). */
 int opadpo_ctx_set_flags(opadpo_ctx* ctx, int gemm_variant, int use_tr);
 /* how the LAST opadpo_seq_logprobs_bwd of this context flushed its LoRA wgrads: 1 = ordered reduce (bit-reproducible), 0 = fp32 atomics
  * (bit 12 set, or lora_r % 256 != 0), -1 = no backward yet */
@@ -484,6 +504,18 @@ int opadpo_saved_residual(opadpo_ctx* ctx, const opadpo_saved* saved, int layer,
 int opadpo_decode_begin(opadpo_ctx* ctx, int adapter_id, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats, int B, int Q,
                         int max_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, int eos_id, int pad_id, int suppress_eos,
                         int32_t* history, void* stream);
+/* policy.generate(do_sample=True, num_return_sequences=n, ...) (rl_models.py respond): opadpo_decode_begin's arguments plus n.  ONE prefill of the B
+ * prompts (passes of at most 64); their KV caches [n_layers, B, heads, Q+575, head_dim] are the shared prefixes of the prompts' n rows, whose
+ * generated keys live in per-row suffix caches [n_layers, B*n, heads, max_new_tokens, head_dim].  Row b = i*n + j is sample j of prompt i and draws
+ * with (seed, step, b), exactly as row b of a rollout over the prompts repeated n times each; history is [max_new_tokens, B*n].  Token 0 comes from
+ * the prompts' last hidden rows expanded to B*n rows: step 0 has the launches and the bits of the repeated-prompt run.  The decode steps use
+ * opadpo_attn_decode_shared (form 0; context flag bit 15: form 1, whose tokens are those of the repeated-prompt rollout).
+ * opadpo_decode_run / _step / _all_finished / _end work per row as after opadpo_decode_begin.  1 <= n <= OPADPO_MAX_RETURN_SEQUENCES and B*n <= 256,
+ * refused with text otherwise; n = 1 IS opadpo_decode_begin (same launches, arena and bits).  Armed logit processors keep their 64-row cap, which
+ * counts B*n rows. */
+int opadpo_decode_begin_n(opadpo_ctx* ctx, int adapter_id, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats, int B, int Q, int n,
+                          int max_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, int eos_id, int pad_id, int suppress_eos,
+                          int32_t* history, void* stream);
 /* Logit bias and first-token scores of the NEXT opadpo_decode_begin of this context (model_vqa_logit.py: sequence_bias / output_scores).
  * bias_ids / bias [n] and score_ids [m] are HOST arrays (copied; n, m <= OPADPO_MAX_LOGIT_IDS, ids in [0, vocab), bias ids distinct).
  * n > 0: every step of that generation - the prefill head that produces token 0 included - adds bias[e] to the logit of bias_ids[e] in every

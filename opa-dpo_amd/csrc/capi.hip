@@ -464,6 +464,27 @@ int opadpo_attn_decode_beam(const uint16_t* qkv, int ld, const float* cos_tab, c
                                       max_new, table, 0, scale, workspace, workspace_bytes, S(stream)),
               fn);
 }
+size_t opadpo_attn_decode_shared_workspace_bytes(int items, int n, int nh, int hd, int Lp, int max_new) {
+  return attn_decode_shared_workspace_bytes(items, n, nh, hd, Lp, max_new);
+}
+int opadpo_attn_decode_shared(const uint16_t* qkv, int ld, const float* cos_tab, const float* sin_tab, const uint16_t* k_prefix,
+                              const uint16_t* v_prefix, uint16_t* k_suffix, uint16_t* v_suffix, uint16_t* o, const uint8_t* prefix_mask, int items,
+                              int n, int nh, int hd, const int32_t* pos_ptr, int Lp, int max_new, float scale, void* workspace,
+                              size_t workspace_bytes, int form, void* stream) {
+  const char* fn = "opadpo_attn_decode_shared";
+  if (!qkv || !cos_tab || !sin_tab || !k_prefix || !v_prefix || !k_suffix || !v_suffix || !o || !pos_ptr) return bad(fn, "null operand");
+  if (n < 1 || n > OPADPO_MAX_RETURN_SEQUENCES) return bad(fn, "num_return_sequences must be in 1..OPADPO_MAX_RETURN_SEQUENCES (16)");
+  if (items <= 0 || nh <= 0 || Lp <= 0 || max_new <= 0) return bad(fn, "bad shape");
+  if (hd != 64 && hd != 128) return bad(fn, "head_dim must be 64 or 128");
+  if (form < 0 || form > 2) return bad(fn, "form must be 0 (the library's choice), 1 (per-row) or 2 (grouped)");
+  if (form == 2 && hd != 128) return bad(fn, "the grouped form (2) needs head_dim 128");
+  if (ld % 8 || ld < 3 * nh * hd) return bad(fn, "qkv rows must hold [q|k|v] with an aligned leading dimension");
+  const size_t need = attn_decode_shared_workspace_bytes(items, n, nh, hd, Lp, max_new);
+  if (need && (!workspace || workspace_bytes < need)) return bad(fn, "workspace smaller than opadpo_attn_decode_shared_workspace_bytes");
+  return done(launch_attn_decode_shared(qkv, ld, cos_tab, sin_tab, k_prefix, v_prefix, k_suffix, v_suffix, o, prefix_mask, items, n, nh, hd, pos_ptr,
+                                        Lp, max_new, scale, workspace, workspace_bytes, form, S(stream)),
+              fn);
+}
 int opadpo_beam_step(const float* logits, int ldl, int B, int k, int V, int step, int max_new, int eos_id, int pad_id, float* run_score,
                      float* cand_val, int32_t* cand_tok, float* fin_score, int32_t* fin_info, int32_t* fin_n, uint8_t* done_, int32_t* cur_tok,
                      int32_t* bp, int32_t* table, void* stream) {

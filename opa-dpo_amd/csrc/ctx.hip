@@ -290,6 +290,7 @@ struct opadpo_ctx {
   bool wgrad_atomic = false;                      // bit 12: the LoRA wgrads keep the fp32-atomic flush
   bool resid_deferred = false;                    // bit 13: residual adds in the RMSNorm that follows, not in the projections' epilogues
   bool swiglu_bwd_own_kernel = false;             // bit 14: SwiGLU backward in its own kernel, not in the dgrad's epilogue
+  bool shared_attn_per_row = false;               // bit 15: the shared-prefix decode attention (opadpo_decode_begin_n) stays per-row
   // live profile of the gemm_nt launches (opadpo_ctx_profile)
   bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
@@ -310,6 +311,9 @@ struct opadpo_ctx {
     // beam decode (opadpo_decode_beam_begin): B = items * beams rows; kc / vc = the items' prefix caches [items, nh, Lp, hd], ks / vs = the
     // rows' suffix caches [B, nh, max_new, hd]; finished = per-item done flags; bs = selection state (decode.hip beam_update_kernel)
     int beams = 0, items = 0; bf16_t *ks = nullptr, *vs = nullptr; BeamState bs{};
+    // n sampled responses per prompt (opadpo_decode_begin_n, nret >= 2): B = items * nret rows on the beam decode's cache layout (kc / vc per item,
+    // ks / vs per row, key_mask [items, Lp]); everything else is the sampling rollout of B rows
+    int nret = 0;
     hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; hipStream_t cap_stream = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;
   } dec;
 };
@@ -703,6 +707,7 @@ int opadpo_ctx_set_flags(opadpo_ctx* c, int gemm_variant, int use_tr) {
   c->wgrad_atomic = bit(12);
   c->resid_deferred = bit(13);
   c->swiglu_bwd_own_kernel = bit(14);
+  c->shared_attn_per_row = bit(15);
   return 0;
 }
 
@@ -1403,6 +1408,11 @@ static hipError_t decode_one(opadpo_ctx* c, hipStream_t st) {
       return launch_attn_decode_beam(b.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * pre, D.vc + i * pre, D.ks + i * suf, D.vs + i * suf, b.attn, D.key_mask,
                                      D.items, D.beams, nh, hd, D.pos_d, D.Lp, D.max_new, D.bs.table, D.bs.table_stride, scale, D.ws, D.ws_bytes, st);
     }
+    if (D.nret) {
+      const size_t pre = (size_t)D.items * nh * D.Lp * hd, suf = (size_t)B * nh * D.max_new * hd;
+      return launch_attn_decode_shared(b.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * pre, D.vc + i * pre, D.ks + i * suf, D.vs + i * suf, b.attn, D.key_mask,
+                                       D.items, D.nret, nh, hd, D.pos_d, D.Lp, D.max_new, scale, D.ws, D.ws_bytes, c->shared_attn_per_row ? 1 : 0, st);
+    }
     const size_t per_layer = (size_t)B * nh * D.max_ctx * hd;
     return launch_attn_decode_fused(b.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * per_layer, D.vc + i * per_layer, b.attn, D.key_mask, B, nh, hd, D.pos_d,
                                     D.max_ctx, scale, D.ws, D.ws_bytes, st);
@@ -1457,26 +1467,28 @@ static hipError_t decode_one(opadpo_ctx* c, hipStream_t st) {
   return decode_head(c, (const float*)cur, nullptr, 0, st);
 }
 
-// beams = 0: sampling rollout of B rows; beams = k: beam search over B items x k rows (the prefill runs on the B items only)
+// beams = 0: sampling rollout of B rows; beams = k: beam search over B items x k rows (the prefill runs on the B items only);
+// nret = n >= 2 (beams = 0): sampling rollout of B items x n rows off one prefill of the items
 static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats, int items,
-                             int Q, int beams, int max_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, int eos_id, int pad_id,
+                             int Q, int beams, int nret, int max_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, int eos_id, int pad_id,
                              int suppress_eos, int32_t* history, hipStream_t st) {
   const opadpo_dims& d = c->d;
   const opadpo_ctx::Adapter& ad = c->adapters[adapter_id];
   const int side = d.image_size / d.patch, P = side * side, H = d.hidden, F = d.ffn, r = d.lora_r, nh = d.n_heads, hd = d.head_dim, V = d.vocab;
-  const int B = beams ? items * beams : items;           // decode rows
+  const int B = beams ? items * beams : nret ? items * nret : items;           // decode rows
+  const bool shared = beams || nret;                     // prefix caches per item + suffix caches per row
   // the prefill of more than 64 queries runs in passes of 64: its scratch (and the 32-bit offsets of its GEMMs) stay those of a 64-query rollout,
   // and every kernel of it computes a row independently of how many rows share the launch - the results are those of one pass
   const int pf_items = std::min(items, 64);
   const int Lp = Q + P - 1, max_ctx = Lp + max_new_tokens, M = pf_items * Lp;
-  const int kv_len = beams ? Lp : max_ctx;                // cache slots per prefill sequence
+  const int kv_len = shared ? Lp : max_ctx;               // cache slots per prefill sequence
   CK(ensure_rope(c, max_ctx, st));
   opadpo_ctx::Decode& D = c->dec;
   D.B = B; D.Lp = Lp; D.max_ctx = max_ctx; D.adapter = adapter_id; D.max_new = max_new_tokens;
   D.history = history; D.temperature = temperature; D.top_k = top_k; D.top_p = top_p; D.seed = seed; D.eos_id = eos_id; D.pad_id = pad_id;
   D.suppress_eos = suppress_eos;
-  D.beams = beams; D.items = items;
-  D.ws_bytes = attn_decode_workspace_bytes(B, nh, hd, max_ctx);
+  D.beams = beams; D.items = items; D.nret = nret;
+  D.ws_bytes = nret ? attn_decode_shared_workspace_bytes(items, nret, nh, hd, Lp, max_new_tokens) : attn_decode_workspace_bytes(B, nh, hd, max_ctx);
   // 9..64 sequences without LoRA tails (adapter-free or merged adapter): the decode GEMM for <= 64 tokens (gemm_nt_dec64x_kernel), the o / down
   // projections K-split into fp32 partial tiles that the following RMSNorm adds.  Measured per decode step against the 8/16-row streaming kernels
   // of the other path: B = 16 4.84 vs 5.15 ms, B = 8 4.12 vs 3.80 ms.  Context flag bit 5 keeps those.
@@ -1489,6 +1501,10 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
     Carve cv(base);
     const size_t kvn = (size_t)d.n_layers * items * nh * kv_len * hd;
     D.kc = cv.take<bf16_t>(kvn); D.vc = cv.take<bf16_t>(kvn); D.key_mask = cv.take<uint8_t>((size_t)items * kv_len);
+    if (nret) {
+      const size_t sn = (size_t)d.n_layers * B * nh * max_new_tokens * hd;
+      D.ks = cv.take<bf16_t>(sn); D.vs = cv.take<bf16_t>(sn);
+    }
     if (beams) {
       const size_t sn = (size_t)d.n_layers * B * nh * max_new_tokens * hd, K2 = 2 * (size_t)beams;
       D.ks = cv.take<bf16_t>(sn); D.vs = cv.take<bf16_t>(sn);
@@ -1550,6 +1566,7 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
     CKD(launch_embed_splice(ids + (size_t)s0 * Q, text_mask + (size_t)s0 * Q, c->embed, feats + (size_t)s0 * P * H, pf.labels, nullptr, pf.x, 1, pf.key_mask, n, Q, P, H,
                             OPADPO_IMAGE_TOKEN, st));
     if (beams) CKD(hipMemcpyAsync(D.key_mask, pf.key_mask, (size_t)items * Lp, hipMemcpyDeviceToDevice, st));    // the prefix mask; suffix keys are all visible (B * k <= 64: one pass)
+    else if (nret) CKD(hipMemcpyAsync(D.key_mask + (size_t)s0 * Lp, pf.key_mask, (size_t)n * Lp, hipMemcpyDeviceToDevice, st));      // the pass's rows of the prefix mask
     else {
       hipLaunchKernelGGL(decode_mask_kernel, g1((size_t)n * max_ctx), dim3(256), 0, st, pf.key_mask, D.key_mask + (size_t)s0 * max_ctx, n, Lp, max_ctx);
       CKD(hipGetLastError());
@@ -1585,6 +1602,9 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
   }
   if (!D.logit.score_ids.empty())
     CKD(hipMemcpyAsync(D.score_ids, D.logit.score_ids.data(), D.logit.score_ids.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  std::vector<int32_t> item_of(nret ? B : 0);              // row b reads item b / n (D.cur_tok is free until the head samples into it)
+  for (int b = 0; b < (int)item_of.size(); ++b) item_of[b] = b / nret;
+  if (nret) CKD(hipMemcpyAsync(D.cur_tok, item_of.data(), item_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
   { const int32_t p0 = Lp - 1; CKD(hipMemcpyAsync(D.pos_d, &p0, sizeof(int32_t), hipMemcpyHostToDevice, st)); CKD(hipStreamSynchronize(st)); }
   // history [max_new, B] starts as pad
   if (history) {
@@ -1593,6 +1613,12 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
     CKD(hipStreamSynchronize(st));
   }
   // token 0 from the prefill logits (beam decode: step 0 of the search on the items' rows)
+  if (nret) {
+    // the items' last hidden rows expanded to B rows (b.h and, after it is read, D.hs are free here), then the head on B rows as a B-row rollout runs it
+    CKD(launch_gather_rows((const bf16_t*)D.hs, 2 * H, D.cur_tok, (bf16_t*)D.b.h, B, 2 * H, st));
+    if (!fr) CKD(launch_gather_rows((const bf16_t*)D.x, 2 * H, D.cur_tok, (bf16_t*)D.hs, B, 2 * H, st));
+    CKD(fr ? decode_head(c, D.b.h, nullptr, 0, st, B) : decode_head(c, D.b.h, D.hs, 1, st, B));
+  } else
   CKD(fr ? decode_head(c, D.hs, nullptr, 0, st, items) : decode_head(c, D.hs, D.x, 1, st, items));
   if (!D.logit.score_ids.empty())          // step-0 scores: D.logits still holds what the sampler just read (bias added, EOS column suppressed)
     CKD(launch_gather_scores(D.logits, V, B, V, D.score_ids, D.logit.score_ids.data(), (int)D.logit.score_ids.size(), D.logit.raw ? 0.f : temperature,
@@ -1617,7 +1643,30 @@ int opadpo_decode_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const
   if (!ids || !text_mask || !feats || !history || B <= 0 || Q <= 0 || max_new_tokens <= 0 || temperature <= 0.f) return cbad(c, __func__, "null operand or bad shape");
   opadpo_decode_end(c);
   c->dec.logit = std::move(arm);
-  return decode_begin_impl(c, __func__, adapter_id, ids, text_mask, feats, B, Q, 0, max_new_tokens, temperature, top_k, top_p, seed, eos_id, pad_id,
+  return decode_begin_impl(c, __func__, adapter_id, ids, text_mask, feats, B, Q, 0, 0, max_new_tokens, temperature, top_k, top_p, seed, eos_id, pad_id,
+                           suppress_eos, history, (hipStream_t)stream);
+}
+
+int opadpo_decode_begin_n(opadpo_ctx* c, int adapter_id, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats, int B, int Q, int n,
+                          int max_new_tokens, float temperature, int top_k, float top_p, uint64_t seed, int eos_id, int pad_id, int suppress_eos,
+                          int32_t* history, void* stream) {
+  if (!c) return (int)hipErrorInvalidValue;
+  if (n == 1) return opadpo_decode_begin(c, adapter_id, ids, text_mask, feats, B, Q, max_new_tokens, temperature, top_k, top_p, seed, eos_id, pad_id,
+                                         suppress_eos, history, stream);
+  // the logit-processor setting is for THIS call, accepted or refused (as in opadpo_decode_begin)
+  opadpo_ctx::LogitArm arm = std::move(c->next_logit);
+  c->next_logit = {};
+  if (n < 1 || n > OPADPO_MAX_RETURN_SEQUENCES) return cbad(c, __func__, "num_return_sequences must be in 1..OPADPO_MAX_RETURN_SEQUENCES (16)");
+  if (B > 0 && (long long)B * n > 256)
+    return cbad(c, __func__, "B * num_return_sequences above 256 rows per device is not supported by the decode GEMMs (opadpo_gemm_nt_decode_wide: M <= 256)");
+  if ((long long)B * n > 64 && (!arm.bias_ids.empty() || !arm.score_ids.empty()))
+    return cbad(c, __func__, "logit bias / first-token scores (opadpo_ctx_set_logit_processors) take at most 64 rows: B * num_return_sequences above 64 is not supported with them");
+  if (!weights_ready(c)) return cbad(c, __func__, "LLM weights not set");
+  if (adapter_id < 0 || adapter_id >= OPADPO_MAX_ADAPTERS) return cbad(c, __func__, "adapter id out of range");
+  if (!ids || !text_mask || !feats || !history || B <= 0 || Q <= 0 || max_new_tokens <= 0 || temperature <= 0.f) return cbad(c, __func__, "null operand or bad shape");
+  opadpo_decode_end(c);
+  c->dec.logit = std::move(arm);
+  return decode_begin_impl(c, __func__, adapter_id, ids, text_mask, feats, B, Q, 0, n, max_new_tokens, temperature, top_k, top_p, seed, eos_id, pad_id,
                            suppress_eos, history, (hipStream_t)stream);
 }
 
@@ -1635,7 +1684,7 @@ int opadpo_decode_beam_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, 
     return cbad(c, __func__, "logit bias / first-token scores (opadpo_ctx_set_logit_processors) are not supported under beam search");
   }
   opadpo_decode_end(c);
-  return decode_begin_impl(c, __func__, adapter_id, ids, text_mask, feats, B, Q, k, max_new_tokens, 1.0f, 0, 1.0f, 0, eos_id, pad_id, 0, nullptr,
+  return decode_begin_impl(c, __func__, adapter_id, ids, text_mask, feats, B, Q, k, 0, max_new_tokens, 1.0f, 0, 1.0f, 0, eos_id, pad_id, 0, nullptr,
                            (hipStream_t)stream);
 }
 
@@ -1763,7 +1812,7 @@ int opadpo_decode_end(opadpo_ctx* c) {
   if (D.graph) { (void)hipGraphDestroy(D.graph); D.graph = nullptr; }
   if (D.cap_stream) { (void)hipStreamSynchronize(D.cap_stream); }
   if (D.active) { ctx_free(c, D.arena, D.bytes); D.arena = nullptr; D.active = false; }
-  D.beams = 0; D.items = 0;
+  D.beams = 0; D.items = 0; D.nret = 0;
   D.logit = {}; D.bias_ids = nullptr; D.score_ids = nullptr; D.bias = nullptr;
   c->next_logit = {};
   return 0;

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "kernels.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -28,7 +29,12 @@ namespace {
 // shared prefix caches [items, nh, Lp, HD] (key_mask [items, Lp]); kc_w / vc_w = the suffix caches [rows, nh, max_new, HD]: the key of suffix
 // slot s = j - Lp of row b lives in physical row table[b][s], and the new token's key is appended at (b, pos - Lp).  The table is
 // double-buffered by the parity of s + 1 for the appended slot s.  The non-beam instantiations (empty pack) are the kernel as it was.
+// SHARED (one SharedDec instead of the BeamDec; n sampled responses per prompt, opadpo_attn_decode_shared): the beam layout with the identity slot
+// table (row b reads and appends its own suffix row; table = nullptr), k = responses per item.  key0 = first key of the launch (0: the whole
+// context, the per-row form, same split rule and key order as the fused kernel; Lp: the suffix part of the grouped form), slots > 0: every block
+// writes its (max, sum, out) partial into slot slot0 + split of the row's `slots` slots, whatever gridDim.z is.
 struct BeamDec { const int32_t* table; long long tstride; int Lp, max_new, k; };
+struct SharedDec : BeamDec { int key0, slots, slot0; };
 template <int HD, int NW, bool FUSE = false, typename... BA>
 __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* q, int ldq, const bf16_t* kc, const bf16_t* vc,
                                                                bf16_t* o, const uint8_t* key_mask, int nh, int ctx_arg,
@@ -36,6 +42,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* q, i
                                                                const float* cosb = nullptr, const float* sinb = nullptr,
                                                                bf16_t* kc_w = nullptr, bf16_t* vc_w = nullptr, BA... beam) {
   constexpr bool BEAM = sizeof...(BA) > 0;
+  constexpr bool SHARED = (std::is_same_v<BA, SharedDec> || ...);
   static_assert(!BEAM || FUSE, "the beam form appends the new token: FUSE only");
   constexpr int LPK = HD / 8;            // lanes per key
   constexpr int KPW = 64 / LPK;          // keys per wave step
@@ -47,8 +54,10 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* q, i
   const int h = blockIdx.x, b = blockIdx.y, split = blockIdx.z, splits = gridDim.z;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane / LPK, d = lane % LPK;
-  const int per = (((ctx + splits - 1) / splits) + NG - 1) / NG * NG;
-  const int s0 = split * per, s1 = min(ctx, s0 + per);
+  int key0 = 0;
+  if constexpr (SHARED) key0 = (beam, ...).key0;
+  const int per = (((ctx - key0 + splits - 1) / splits) + NG - 1) / NG * NG;
+  const int s0 = key0 + split * per, s1 = min(ctx, s0 + per);
 
   float qf[8];
   const int pos = FUSE ? ctx - 1 : -1;                 // slot of the token this step appends
@@ -85,7 +94,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* q, i
     const size_t pseq = ((size_t)(b / bm.k) * nh + h) * bm.Lp;
     kpb = kc + pseq * HD + d * 8; vpb = vc + pseq * HD + d * 8;
     kmb = key_mask ? key_mask + (size_t)(b / bm.k) * bm.Lp : nullptr;
-    tbl = bm.table + (size_t)((pos - bm.Lp + 1) & 1) * bm.tstride + (size_t)b * bm.max_new;
+    if constexpr (!SHARED) tbl = bm.table + (size_t)((pos - bm.Lp + 1) & 1) * bm.tstride + (size_t)b * bm.max_new;
   }
 
   float m = -1.0e30f, l = 0.f, acc[8];
@@ -110,7 +119,9 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* q, i
           const bf16_t* vp = vpb + (size_t)j * HD;
           if (j >= bm.Lp) {
             const int sl = j - bm.Lp;
-            const size_t r = (((size_t)tbl[sl] * nh + h) * bm.max_new + sl) * HD + d * 8;
+            size_t prow = b;
+            if constexpr (!SHARED) prow = tbl[sl];
+            const size_t r = ((prow * nh + h) * bm.max_new + sl) * HD + d * 8;
             kp = kc_w + r; vp = vc_w + r;
           }
           const u4n_t a = __builtin_nontemporal_load((const u4n_t*)kp), c = __builtin_nontemporal_load((const u4n_t*)vp);
@@ -199,10 +210,15 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* q, i
       O += sm_acc[i][tid] * w;
     }
     const int bh = b * nh + h;
-    if (splits == 1) {
+    int slots = splits, slot = split;
+    if constexpr (SHARED) {
+      const SharedDec sd = (beam, ...);
+      if (sd.slots > 0) { slots = sd.slots; slot = sd.slot0 + split; }
+    }
+    if (slots == 1) {
       o[(size_t)bh * HD + tid] = f2bf(Lsum > 0.f ? O / Lsum : 0.f);
     } else {
-      float* part = ws_part + ((size_t)bh * splits + split) * (HD + 2);
+      float* part = ws_part + ((size_t)bh * slots + slot) * (HD + 2);
       part[2 + tid] = O;
       if (tid == 0) { part[0] = M; part[1] = Lsum; }
     }
@@ -223,6 +239,199 @@ __global__ void attn_decode_merge_kernel(const float* ws_part, bf16_t* o, int sp
     OO += pi[2 + tid] * w;
   }
   o[(size_t)bh * HD + tid] = f2bf(LL > 0.f ? OO / LL : 0.f);
+}
+
+// ---- grouped shared-prefix decode attention (num_return_sequences: n sampled responses per prompt; head_dim 128) -------------------------
+// The n <= 16 rows of an item attend the SAME prefix keys, and a launch costs the bytes through a CU's vector-memory pipe whatever their source
+// (DESIGN.md §4), so one workgroup owns (item, head, prefix key range), brings every K / V tile in ONCE and uses it against all n query rows,
+// padded to one 16-row MFMA tile.  grid = (nh, items, ranges), 4 waves; wave w takes the 64-key tiles w, w + 4, .. of the range:
+//   S^T[key][q] = K . Q^T    v_mfma_f32_16x16x32_bf16, A = K fragment (lane c = lane & 15 holds 16 consecutive bytes of key c, straight from the
+//                            head-major cache, no LDS), B = the rotated q rows (rotation at pos = pos_ptr[0], rounded to bf16 as the per-row form
+//                            rounds them); the accumulator has the query row on lane & 15 and 4 keys in its registers
+//   O^T[d][q] += V^T . P^T   two 16-key accumulator tiles packed to bf16 ARE the B operand of a 32-key step (no lane movement); V is staged in the
+//                            wave's own swizzled LDS tile and read transposed (ds_read_b64_tr_b16), the idiom of attention.hip
+// Online softmax per query row in fp32 (log2 units); P is rounded to bf16 for the P.V MFMA - the one rounding point this form adds over the
+// per-row form.  The waves' (m, l, O) merge through LDS and go out as partials in attn_decode_merge_kernel's format, slot = range index of the
+// row's `slots` slots: plain vector stores, no atomics; the suffix launch fills the last slot and the merge is its own launch.
+constexpr int GRP_W = 4, GRP_TILE = 64 * 128 * 2;
+__device__ __forceinline__ int grp_at(int row, int byte) { return row * 256 + ((((byte >> 4) ^ ((row & 7) << 1))) << 4) + (byte & 15); }
+
+__global__ __launch_bounds__(GRP_W * 64) void attn_decode_group_kernel(const bf16_t* qkv, int ld, const float* cosb, const float* sinb, const bf16_t* kp,
+                                                                       const bf16_t* vp, const uint8_t* prefix_mask, int n, int nh,
+                                                                       const int32_t* pos_ptr, int Lp, int per, int slots, float scale_log2e,
+                                                                       float* ws_part) {
+  constexpr int HD = 128;
+  typedef __attribute__((ext_vector_type(4))) unsigned u4n_t;
+  __shared__ __attribute__((aligned(16))) char smem[GRP_W * GRP_TILE];
+  const int h = blockIdx.x, item = blockIdx.y, rg = blockIdx.z;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
+  const int pos = pos_ptr[0];
+  const int k_lo = rg * per, k_hi = min(Lp, k_lo + per);        // the host cuts the ranges so that none is empty
+  const int ntiles = max(0, (k_hi - k_lo + 63) / 64), trips = (ntiles + GRP_W - 1) / GRP_W;
+  // q fragments: B[k = 8g + j][col = c] = rotated q of row item * n + c at d = kk * 32 + 8g + j (rows >= n: zeros)
+  bf16x8_t qf[4];
+  {
+    const bf16_t* qrow = qkv + (size_t)(item * n + min(c, n - 1)) * ld + h * HD;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      constexpr int half = HD / 2;
+      const int d0 = kk * 32 + g * 8;
+      const bool lo = d0 < half;
+      const int i0 = lo ? d0 : d0 - half;
+      float own[8], oth[8], out[8];
+      unpack8(*(const uint4*)(qrow + d0), own);
+      unpack8(*(const uint4*)(qrow + (lo ? d0 + half : d0 - half)), oth);
+      const float* cp = cosb + (size_t)pos * half + i0;
+      const float* sp = sinb + (size_t)pos * half + i0;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) out[e] = lo ? own[e] * cp[e] - oth[e] * sp[e] : own[e] * cp[e] + oth[e] * sp[e];
+      uint4 rb = pack8(out);
+      if (c >= n) rb = make_uint4(0, 0, 0, 0);
+      qf[kk] = *(const bf16x8_t*)&rb;
+    }
+  }
+  const size_t pseq = ((size_t)item * nh + h) * Lp;
+  const bf16_t* kb = kp + pseq * HD;
+  const bf16_t* vb = vp + pseq * HD;
+  const uint8_t* km = prefix_mask ? prefix_mask + (size_t)item * Lp : nullptr;
+  char* const Vs = smem + wave * GRP_TILE;
+
+  // a tile's loads: K fragments [16-key block kf][k-step kk], V rows i * 4 + g (16-byte chunk c), the lane's 16 visibility bits (key kf*16 + g*4 + r).
+  // Keys behind the range end are clamped to its last key (never read out of bounds) and masked.
+  uint4 kreg[4][4], vreg[16];
+  uint32_t okreg = 0;
+  auto fetch = [&](int t) {
+    okreg = 0;
+    if (t >= ntiles) return;                     // wave-uniform
+    const int k0 = k_lo + t * 64;
+#pragma unroll
+    for (int kf = 0; kf < 4; ++kf) {
+      const bf16_t* row = kb + (size_t)min(k0 + kf * 16 + c, k_hi - 1) * HD + g * 8;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const u4n_t a = __builtin_nontemporal_load((const u4n_t*)(row + kk * 32));
+        kreg[kf][kk] = make_uint4(a.x, a.y, a.z, a.w);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const u4n_t a = __builtin_nontemporal_load((const u4n_t*)(vb + (size_t)min(k0 + i * 4 + g, k_hi - 1) * HD + c * 8));
+      vreg[i] = make_uint4(a.x, a.y, a.z, a.w);
+    }
+#pragma unroll
+    for (int kf = 0; kf < 4; ++kf)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = k0 + kf * 16 + g * 4 + r;
+        const bool ok = key < k_hi && (!km || km[min(key, k_hi - 1)]);
+        okreg |= (ok ? 1u : 0u) << (kf * 4 + r);
+      }
+  };
+
+  float m_run = -1.0e30f, l_run = 0.f;
+  f32x4_t o[8];
+#pragma unroll
+  for (int d = 0; d < 8; ++d) o[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  fetch(wave);
+  for (int trip = 0; trip < trips; ++trip) {
+    const int t = trip * GRP_W + wave;
+    const bool live = t < ntiles;                // wave-uniform
+    uint4 kcur[4][4];
+    const uint32_t okb = okreg;
+    if (live) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) *(uint4*)(Vs + grp_at(i * 4 + g, c * 16)) = vreg[i];
+#pragma unroll
+      for (int kf = 0; kf < 4; ++kf)
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) kcur[kf][kk] = kreg[kf][kk];
+    }
+    __syncthreads();
+    if (trip + 1 < trips) fetch(t + GRP_W);      // the next tile's loads fly while this one is consumed
+    if (live) {
+      f32x4_t sc[4];
+#pragma unroll
+      for (int kf = 0; kf < 4; ++kf) {
+        sc[kf] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+          sc[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)&kcur[kf][kk], qf[kk], sc[kf], 0, 0, 0);
+      }
+      // sc[kf][r] = S^T[key = kf*16 + g*4 + r][q = c]
+      float mx = -1.0e30f;
+#pragma unroll
+      for (int kf = 0; kf < 4; ++kf)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          sc[kf][r] = (okb >> (kf * 4 + r) & 1u) ? sc[kf][r] * scale_log2e : -INFINITY;      // exp2(-inf - m) = 0 (m stays finite)
+          mx = fmaxf(mx, sc[kf][r]);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float m_new = fmaxf(m_run, mx);
+      float psum = 0.f;
+#pragma unroll
+      for (int kf = 0; kf < 4; ++kf)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float pv = fast_exp2(sc[kf][r] - m_new);
+          sc[kf][r] = pv;
+          psum += pv;
+        }
+      const float alpha = fast_exp2(m_run - m_new);
+      l_run = l_run * alpha + psum;
+      m_run = m_new;
+#pragma unroll
+      for (int d = 0; d < 8; ++d) { o[d][0] *= alpha; o[d][1] *= alpha; o[d][2] *= alpha; o[d][3] *= alpha; }
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        union { bf16x8_t v; uint32_t w[4]; } pf;
+        pf.w[0] = pack_bf2(sc[2 * ks][0], sc[2 * ks][1]); pf.w[1] = pack_bf2(sc[2 * ks][2], sc[2 * ks][3]);
+        pf.w[2] = pack_bf2(sc[2 * ks + 1][0], sc[2 * ks + 1][1]); pf.w[3] = pack_bf2(sc[2 * ks + 1][2], sc[2 * ks + 1][3]);
+        const int r0 = (2 * ks) * 16 + g * 4 + (c >> 2), r1 = r0 + 16;
+#pragma unroll
+        for (int d = 0; d < 8; ++d) {
+          // A[row = c][k = j]: V[key r0 + j][d * 16 + c] (j < 4), V[key r1 + j - 4][d * 16 + c] - the keys the lane's P registers hold
+          union { bf16x8_t v; s16x4_t hh[2]; } vf;
+          const int byte = (d * 16 + (c & 3) * 4) * 2;
+          vf.hh[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, Vs + grp_at(r0, byte)));
+          vf.hh[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, Vs + grp_at(r1, byte)));
+          o[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf.v, pf.v, o[d], 0, 0, 0);
+        }
+      }
+    }
+    __syncthreads();
+  }
+  l_run += __shfl_xor(l_run, 16, 64);
+  l_run += __shfl_xor(l_run, 32, 64);
+  // the four waves' partials of row c: [wave][row][m, l, O[HD]] over the V tiles (every wave is past its last read: the loop ends on a barrier)
+  float* const red = (float*)smem;
+  {
+    float* mine = red + (size_t)(wave * 16 + c) * (HD + 2);
+    if (g == 0) { mine[0] = m_run; mine[1] = l_run; }
+#pragma unroll
+    for (int d = 0; d < 8; ++d)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mine[2 + d * 16 + g * 4 + r] = o[d][r];      // o[d][r] = O^T[d*16 + g*4 + r][q = c]
+  }
+  __syncthreads();
+  for (int idx = tid; idx < n * HD; idx += GRP_W * 64) {
+    const int row = idx / HD, d = idx % HD;
+    float M = -1.0e30f;
+#pragma unroll
+    for (int w = 0; w < GRP_W; ++w) M = fmaxf(M, red[(size_t)(w * 16 + row) * (HD + 2)]);
+    float L = 0.f, O = 0.f;
+#pragma unroll
+    for (int w = 0; w < GRP_W; ++w) {
+      const float* pw = red + (size_t)(w * 16 + row) * (HD + 2);
+      const float wt = fast_exp2(pw[0] - M);
+      L += pw[1] * wt;
+      O += pw[2 + d] * wt;
+    }
+    float* part = ws_part + ((size_t)((item * n + row) * nh + h) * slots + rg) * (HD + 2);
+    part[2 + d] = O;
+    if (d == 0) { part[0] = M; part[1] = L; }
+  }
 }
 
 // ---- decode-step RoPE + KV-cache append: q rotated in place, k rotated into k_cache[b,h,pos,:], v copied into
@@ -1022,6 +1231,70 @@ hipError_t launch_attn_decode_beam(const bf16_t* qkv, int ld, const float* cosb,
   else           { if (fat) ADB(64, 16); else ADB(64, 4); }
 #undef ADB
   if (splits > 1) hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(rows * nh), dim3(hd), 0, st, part, o, splits, hd);
+  return hipGetLastError();
+}
+
+// ---- n sampled responses per prompt: row b = sample b % n of item b / n; prefix caches per item, suffix caches per row ------------------------
+// prefix key ranges of the grouped form: items * nh * ranges fills about ONE round of the 256 CUs; the stride from one range to the next is a
+// multiple of 64 keys (one tile per wave step, at least 64), the last range holds the remainder (1 .. stride keys), and no range is empty
+static int attn_decode_shared_ranges(int items, int nh, int Lp, int* per_out) {
+  int R = std::max(1, 256 / std::max(1, items * nh));
+  R = std::min(R, std::max(1, Lp / 64));
+  const int per = ((Lp + R - 1) / R + 63) / 64 * 64;
+  if (per_out) *per_out = per;
+  return (Lp + per - 1) / per;
+}
+// the library's choice (form 0): the grouped form for n >= 2 at head_dim 128.  Measured at 7B, Lp = 703 (profiles/shared_prefix_bench_7b.json):
+// 5.04 against 6.68 ms per decode step at 8 x 8 rows, 7.09 against 8.50 with 896 new tokens, 9.48 against 17.98 at 16 x 16 rows - the grouped form
+// wins at every measured shape; n = 2..7 and other head counts are not measured and follow the byte count (the prefix moves once per item).
+static bool attn_decode_shared_grouped(int n, int hd, int form) { return form == 2 || (form == 0 && n >= 2 && hd == 128); }
+size_t attn_decode_shared_workspace_bytes(int items, int n, int nh, int hd, int Lp, int max_new) {
+  if (items <= 0 || n <= 0) return 0;
+  size_t bytes = attn_decode_workspace_bytes(items * n, nh, hd, Lp + max_new);          // per-row form: the fused kernel's key ranges
+  if (hd == 128) {
+    const int R = attn_decode_shared_ranges(items, nh, Lp, nullptr);
+    bytes = std::max(bytes, (size_t)items * n * nh * (R + 1) * (hd + 2) * 4);           // grouped form: R prefix slots + the suffix slot
+  }
+  return bytes;
+}
+
+hipError_t launch_attn_decode_shared(const bf16_t* qkv, int ld, const float* cosb, const float* sinb, const bf16_t* kp, const bf16_t* vp, bf16_t* ks,
+                                     bf16_t* vs, bf16_t* o, const uint8_t* prefix_mask, int items, int n, int nh, int hd, const int32_t* pos_ptr, int Lp,
+                                     int max_new, float scale, void* workspace, size_t workspace_bytes, int form, hipStream_t st) {
+  const int rows = items * n, max_ctx = Lp + max_new;
+  if (rows <= 0) return hipSuccess;
+  if ((hd != 64 && hd != 128) || !pos_ptr || ld % 8 || n <= 0 || n > OPADPO_MAX_RETURN_SEQUENCES || form < 0 || form > 2) return hipErrorInvalidValue;
+  float* part = (float*)workspace;
+  const float sl2 = scale * 1.4426950408889634f;
+#define ADS(HD_, NW_, GRID_, SD_) hipLaunchKernelGGL((attn_decode_kernel<HD_, NW_, true, SharedDec>), GRID_, dim3(NW_ * 64), 0, st, qkv, ld, kp, vp, o, prefix_mask, nh, 0, \
+                                                     pos_ptr, max_ctx, sl2, part, cosb, sinb, ks, vs, SD_)
+  if (!attn_decode_shared_grouped(n, hd, form)) {
+    // per-row form: the beam kernel with the identity slot table - the split rule and the key order of the fused kernel on a materialised cache
+    int splits = attn_decode_splits(rows, nh, max_ctx);
+    if (splits > 1 && (!workspace || workspace_bytes < attn_decode_workspace_bytes(rows, nh, hd, max_ctx))) splits = 1;
+    const bool fat = attn_decode_fat(rows, nh, splits);
+    const dim3 gr(nh, rows, splits);
+    const SharedDec sd{{nullptr, 0, Lp, max_new, n}, 0, 0, 0};
+    if (hd == 128) { if (fat) ADS(128, 16, gr, sd); else ADS(128, 4, gr, sd); }
+    else           { if (fat) ADS(64, 16, gr, sd); else ADS(64, 4, gr, sd); }
+    if (splits > 1) hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(rows * nh), dim3(hd), 0, st, part, o, splits, hd);
+    return hipGetLastError();
+  }
+  if (hd != 128) return hipErrorInvalidValue;
+  int per = 0;
+  const int R = attn_decode_shared_ranges(items, nh, Lp, &per), slots = R + 1;
+  if (!workspace || workspace_bytes < (size_t)rows * nh * slots * (hd + 2) * 4) return hipErrorInvalidValue;
+  // 1. the suffix keys [Lp, pos] of every row, the new token rotated and appended (the per-row kernel, one key range) -> slot R
+  {
+    const dim3 gr(nh, rows, 1);
+    const SharedDec sd{{nullptr, 0, Lp, max_new, n}, Lp, slots, R};
+    if (attn_decode_fat(rows, nh, 1)) ADS(128, 16, gr, sd); else ADS(128, 4, gr, sd);
+  }
+#undef ADS
+  // 2. the items' prefix keys, each tile once for the item's n rows -> slots 0 .. R-1;  3. the merge
+  hipLaunchKernelGGL(attn_decode_group_kernel, dim3(nh, items, R), dim3(GRP_W * 64), 0, st, qkv, ld, cosb, sinb, kp, vp, prefix_mask, n, nh, pos_ptr, Lp, per,
+                     slots, sl2, part);
+  hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(rows * nh), dim3(hd), 0, st, part, o, slots, hd);
   return hipGetLastError();
 }
 

@@ -248,6 +248,11 @@ hipError_t launch_attn_decode_beam(const bf16_t* qkv, int ld, const float* cosb,
                                    bf16_t* vs, bf16_t* o, const uint8_t* prefix_mask, int items, int k, int nh, int hd, const int32_t* pos_ptr, int Lp,
                                    int max_new, const int32_t* table, long long table_stride, float scale, void* workspace, size_t workspace_bytes,
                                    hipStream_t st);
+// n sampled responses per prompt (include/opadpo_hip.h opadpo_attn_decode_shared): form 0 = the library's choice, 1 = per-row, 2 = grouped
+size_t attn_decode_shared_workspace_bytes(int items, int n, int nh, int hd, int Lp, int max_new);
+hipError_t launch_attn_decode_shared(const bf16_t* qkv, int ld, const float* cosb, const float* sinb, const bf16_t* kp, const bf16_t* vp, bf16_t* ks,
+                                     bf16_t* vs, bf16_t* o, const uint8_t* prefix_mask, int items, int n, int nh, int hd, const int32_t* pos_ptr, int Lp,
+                                     int max_new, float scale, void* workspace, size_t workspace_bytes, int form, hipStream_t st);
 // device state of a beam search over items x k rows (rows = items * k; include/opadpo_hip.h opadpo_beam_step lists the shapes)
 struct BeamState {
   float* run_score; float* cand_val; int32_t* cand_tok; float* fin_score; int32_t* fin_info; int32_t* fin_n; uint8_t* done;

@@ -40,6 +40,8 @@ def rollout_parser() -> argparse.ArgumentParser:
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--top_k", type=int, default=30)
     ap.add_argument("--top_p", type=float, default=0.95)
+    ap.add_argument("--num_return_sequences", type=int, default=1,
+                    help="sampled responses per query off one prefill (1..16, per-device batch x N <= 256; the reference hard-codes 1)")
     ap.add_argument("--sample_num", type=int, default=0, help="use only the first N rows (0 = all)")
     ap.add_argument("--max_step", type=int, default=0, help="stop after N rollout steps (0 = whole dataset)")
     ap.add_argument("--image_aspect_ratio", default="pad")
@@ -129,6 +131,9 @@ def run_rollout(args, feedback: Optional[Callable] = None, log=print) -> List[st
     from .online_generate import generator_sampler, rollout_step
     from .rollout_data import QueryResponseDataset, collate_query_response
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
+    nret = int(getattr(args, "num_return_sequences", 1))
+    if not 1 <= nret <= 16 or args.rollout_per_device_batch_size * nret > 256:
+        raise SystemExit(f"--num_return_sequences must be in 1..16 with rollout_per_device_batch_size x N <= 256 (got {nret})")
     none = args.policy_model_name_or_path in (None, "", "none")
     engine, adapter, tok = _engine(args.base_model_name, args.synthetic, None if none else args.policy_model_name_or_path,
                                    args.lora_rank, args.lora_alpha, args.seed)
@@ -143,7 +148,7 @@ def run_rollout(args, feedback: Optional[Callable] = None, log=print) -> List[st
     ds = QueryResponseDataset(rows, tok, args.query_len, image_size=engine.d.image_size, pad_to_square=args.image_aspect_ratio == "pad", log=log)
     gen = Generator(engine, adapter, merge_adapter=True, fuse_swiglu=True)
     sample = generator_sampler(gen, response_len=args.response_len, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-                               seed=args.seed + 1000 * rank)
+                               seed=args.seed + 1000 * rank, num_return_sequences=nret)
     mine = list(range(rank, len(ds), world))
     per_step = max(args.rollout_per_device_batch_size, args.rollout_batch_size // world)
     files = []
@@ -153,8 +158,8 @@ def run_rollout(args, feedback: Optional[Callable] = None, log=print) -> List[st
         idx = mine[s0:s0 + per_step]
         batches = [collate_query_response([ds[j] for j in idx[b0:b0 + args.rollout_per_device_batch_size]])
                    for b0 in range(0, len(idx), args.rollout_per_device_batch_size)]
-        files.append(write_rollout_json(args.output_dir, step, rollout_step(batches, tok, sample, feedback), rank=rank))
-        log(f"step {step}: {len(idx)} rollouts -> {files[-1]}")
+        files.append(write_rollout_json(args.output_dir, step, rollout_step(batches, tok, sample, feedback, num_return_sequences=nret), rank=rank))
+        log(f"step {step}: {len(idx) * nret} rollouts -> {files[-1]}")
     return files
 
 

@@ -283,9 +283,13 @@ class CtxEngine(LlavaEngine):
     @torch.no_grad()
     def generate(self, adapter, queries: torch.Tensor, query_attn_masks: torch.Tensor, image_feats: torch.Tensor, *, max_new_tokens: int,
                  temperature: float, top_k: int, top_p: float, seed: int, eos_token_id: int, pad_token_id: int, suppress_eos: bool,
-                 use_graph: bool, logit_bias: Optional[Dict[int, float]] = None, score_ids: Optional[Sequence[int]] = None):
+                 use_graph: bool, logit_bias: Optional[Dict[int, float]] = None, score_ids: Optional[Sequence[int]] = None,
+                 num_return_sequences: int = 1):
         """-> responses [B, max_new_tokens] int64 (pad after a row finished); prefill, KV cache and the per-token launch loop (or hipGraph) live in
         the context (opadpo_decode_begin / opadpo_decode_run).
+        num_return_sequences = n > 1 (HF generate(do_sample=True, num_return_sequences=n)): n sampled responses per prompt off ONE prefill,
+        responses [B * n, max_new_tokens] item-major (row i * n + j = sample j of prompt i, drawn with (seed, step, row) as row i * n + j of a
+        rollout over queries.repeat_interleave(n, 0)); 1 <= n <= 16 and B * n <= 256 (opadpo_decode_begin_n); scores are [B * n, m].
         logit_bias {token id: bias}: added to that token's logit in every row at every step, before temperature / top-k / top-p (HF
         `sequence_bias` with one-token sequences; at most 64 entries).  An empty dict is no bias: the launches of a call without the keyword.
         score_ids (at most 64 token ids, repeats allowed): the return value becomes (responses, scores [B, len(score_ids)] fp32), the
@@ -295,6 +299,8 @@ class CtxEngine(LlavaEngine):
         greedy and runs it as top_k = 1): the scores are then logit + bias, nothing divided and nothing cut."""
         dev, d = self.dev, self.d
         B, Q = queries.shape
+        nret = int(num_return_sequences)
+        rows = B * max(nret, 1)
         greedy = temperature == 0
         if greedy:
             temperature, top_k, top_p = 1.0, 1, 1.0
@@ -312,18 +318,22 @@ class CtxEngine(LlavaEngine):
         ids = queries.to(dev).to(torch.int32).contiguous()
         tmask = query_attn_masks.to(dev).to(torch.uint8).contiguous()
         feats = image_feats.contiguous()
-        history = torch.empty(max_new_tokens, B, dtype=torch.int32, device=dev)
+        history = torch.empty(max_new_tokens, rows, dtype=torch.int32, device=dev)
         st = L.stream()
         if bias or sids:
             n, m = len(bias), len(sids or ())
-            scores = torch.empty(B, m, dtype=torch.float32, device=dev) if m else None
+            scores = torch.empty(rows, m, dtype=torch.float32, device=dev) if m else None
             self._call("opadpo_ctx_set_logit_processors", (C.c_int32 * n)(*bias.keys()), (C.c_float * n)(*bias.values()), n,
                        (C.c_int32 * m)(*(sids or ())), m, _ptr(scores), int(greedy))
         elif sids is not None:
-            scores = torch.empty(B, 0, dtype=torch.float32, device=dev)
+            scores = torch.empty(rows, 0, dtype=torch.float32, device=dev)
         try:
-            self._call("opadpo_decode_begin", slot, _ptr(ids), _ptr(tmask), _ptr(feats), B, Q, int(max_new_tokens), float(temperature), int(top_k),
-                       float(top_p), int(seed), int(eos_token_id), int(pad_token_id), int(suppress_eos), _ptr(history), st)
+            if nret == 1:
+                self._call("opadpo_decode_begin", slot, _ptr(ids), _ptr(tmask), _ptr(feats), B, Q, int(max_new_tokens), float(temperature), int(top_k),
+                           float(top_p), int(seed), int(eos_token_id), int(pad_token_id), int(suppress_eos), _ptr(history), st)
+            else:       # the bounds on n and B * n are the library's: refused with text
+                self._call("opadpo_decode_begin_n", slot, _ptr(ids), _ptr(tmask), _ptr(feats), B, Q, nret, int(max_new_tokens), float(temperature),
+                           int(top_k), float(top_p), int(seed), int(eos_token_id), int(pad_token_id), int(suppress_eos), _ptr(history), st)
             left = max_new_tokens - 1
             fin = C.c_int(0)
             while left > 0:

@@ -74,9 +74,11 @@ class Generator:
                  image_feats: Optional[torch.Tensor] = None, max_new_tokens: int, temperature: float = 1.0, top_k: int = 0,
                  top_p: float = 1.0, seed: int = 0, eos_token_id: int = EOS_ID, pad_token_id: int = PAD_ID,
                  suppress_eos: bool = False, num_beams: int = 1, logit_bias: Optional[Dict[int, float]] = None,
-                 score_ids: Optional[Sequence[int]] = None):
+                 score_ids: Optional[Sequence[int]] = None, num_return_sequences: int = 1):
         """-> responses [B, max_new_tokens] int64 (pad after a row finished).  num_beams > 1: beam search (HF num_beams, do_sample=False;
         temperature / top_k / top_p / seed are not used), the best hypothesis per query.
+        num_return_sequences = n > 1 (context engine only; ctx.CtxEngine.generate documents it): n sampled responses per prompt off one prefill,
+        responses [B * n, max_new_tokens], row i * n + j = sample j of prompt i.
         logit_bias / score_ids (context engine only; ctx.CtxEngine.generate documents them): an additive bias on single tokens' logits at every
         step, and the first generated token's processed scores at score_ids - the return value is then (responses, scores [B, m])."""
         eng, d, b = self.engine, self.engine.d, self.engine.base
@@ -88,6 +90,13 @@ class Generator:
             if num_beams > 1:
                 raise NotImplementedError("logit_bias / score_ids are not supported under beam search (CtxEngine.generate_beams); the context engine "
                                           "applies them to the sampling / greedy rollout (num_beams = 1)")
+        if num_return_sequences != 1:
+            if not hasattr(eng, "ctx"):
+                raise NotImplementedError("num_return_sequences > 1 runs on the context engine (CtxEngine) only; the op-level LlavaEngine path is a "
+                                          "cross-check of the one-sample rollout")
+            if num_beams > 1:
+                raise NotImplementedError("num_return_sequences > 1 is not supported under beam search: the context engine draws the n responses "
+                                          "of a prompt with the sampling rollout (num_beams = 1)")
         if num_beams > 1 and not hasattr(eng, "ctx"):
             raise NotImplementedError("beam search runs on the context engine (CtxEngine) only; the op-level LlavaEngine path is a cross-check of "
                                       "the sampling rollout")
@@ -95,6 +104,8 @@ class Generator:
             if image_feats is None:
                 image_feats = eng.encode_images(images)
             extra = {} if not logit_bias and score_ids is None else dict(logit_bias=logit_bias, score_ids=score_ids)
+            if num_return_sequences != 1:
+                extra["num_return_sequences"] = int(num_return_sequences)
             if num_beams > 1:
                 return eng.generate_beams(self.adapter, queries, query_attn_masks, image_feats, num_beams=num_beams, max_new_tokens=max_new_tokens,
                                           eos_token_id=eos_token_id, pad_token_id=pad_token_id, use_graph=self.use_graph)[0]
@@ -224,8 +235,10 @@ class Generator:
         return history.t().contiguous().to(torch.int64)
 
     def rollout(self, queries, query_attn_masks, images, *, response_len: int, temperature: float = 1.0, top_k: int = 30,
-                top_p: float = 0.95, seed: int = 0, additional_stop_ids: Sequence[int] = (1577, 29973)) -> torch.Tensor:
-        """Online_Generator.rollout's tensor part (online_generator.py:292-323): sample, then cut at EOS / '?'."""
+                top_p: float = 0.95, seed: int = 0, additional_stop_ids: Sequence[int] = (1577, 29973), num_return_sequences: int = 1) -> torch.Tensor:
+        """Online_Generator.rollout's tensor part (online_generator.py:292-323): sample, then cut at EOS / '?'.  num_return_sequences = n > 1:
+        [B * n, response_len], row i * n + j = sample j of query i."""
+        extra = {} if num_return_sequences == 1 else dict(num_return_sequences=int(num_return_sequences))
         resp = self.generate(queries, query_attn_masks, images, max_new_tokens=response_len, temperature=temperature,
-                             top_k=top_k, top_p=top_p, seed=seed)
+                             top_k=top_k, top_p=top_p, seed=seed, **extra)
         return truncate_after_eos_with_padding(resp, EOS_ID, PAD_ID, list(additional_stop_ids))

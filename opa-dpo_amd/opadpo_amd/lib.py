@@ -73,6 +73,7 @@ SIGNATURES = {
     "opadpo_logit_bias_add": [_p, _i, _i, _i, _p, _p, _p, _i, _p],
     "opadpo_gather_scores": [_p, _i, _i, _i, _p, _p, _i, _f, _i, _f, _p, _p],
     "opadpo_attn_decode_beam": [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _f, _p, _sz, _p],
+    "opadpo_attn_decode_shared": [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _f, _p, _sz, _i, _p],
     "opadpo_beam_step": [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
 }
 # context API (include/opadpo_hip.h, "Context API"): sequence-level entry points on an opaque opadpo_ctx*
@@ -97,6 +98,7 @@ SIGNATURES.update({
     "opadpo_saved_residual": [_p, _p, _i, _p, _p, _p],
     "opadpo_ctx_set_logit_processors": [_p, _p, _p, _i, _p, _i, _p, _i],
     "opadpo_decode_begin": [_p, _i, _p, _p, _p, _i, _i, _i, _f, _i, _f, _u64, _i, _i, _i, _p, _p],
+    "opadpo_decode_begin_n": [_p, _i, _p, _p, _p, _i, _i, _i, _i, _f, _i, _f, _u64, _i, _i, _i, _p, _p],
     "opadpo_decode_step": [_p, _p],
     "opadpo_decode_run": [_p, _i, _i, _p],
     "opadpo_decode_all_finished": [_p, _p, _p],
@@ -107,7 +109,8 @@ SIGNATURES.update({
     "opadpo_reduce_scatter_grads": [_p, _p, _p, _sz, _i, _p],
     "opadpo_all_gather_params": [_p, _p, _p, _sz, _i, _p],
 })
-OTHER_SYMBOLS = ["opadpo_abi_version", "opadpo_last_error", "opadpo_set_flags", "opadpo_attn_decode_workspace_bytes", "opadpo_gemm_tn_group_workspace_bytes",
+OTHER_SYMBOLS = ["opadpo_abi_version", "opadpo_last_error", "opadpo_set_flags", "opadpo_attn_decode_workspace_bytes", "opadpo_attn_decode_shared_workspace_bytes",
+                 "opadpo_gemm_tn_group_workspace_bytes",
                  "opadpo_ctx_destroy", "opadpo_ctx_last_error", "opadpo_ctx_bytes_peak", "opadpo_ctx_wgrad_deterministic"]
 
 _lib: Optional[C.CDLL] = None
@@ -142,6 +145,9 @@ def load() -> C.CDLL:
     lib.opadpo_set_flags.restype = None
     lib.opadpo_attn_decode_workspace_bytes.argtypes = [_i, _i, _i, _i]
     lib.opadpo_attn_decode_workspace_bytes.restype = _sz
+    if hasattr(lib, "opadpo_attn_decode_shared_workspace_bytes"):
+        lib.opadpo_attn_decode_shared_workspace_bytes.argtypes = [_i, _i, _i, _i, _i, _i]
+        lib.opadpo_attn_decode_shared_workspace_bytes.restype = _sz
     if hasattr(lib, "opadpo_gemm_tn_group_workspace_bytes"):
         lib.opadpo_gemm_tn_group_workspace_bytes.argtypes = [_i, _i, _p, _p, _p]
         lib.opadpo_gemm_tn_group_workspace_bytes.restype = _sz

@@ -36,43 +36,53 @@ def decode_batch(tokenizer, ids: torch.Tensor) -> List[str]:
 
 
 def rollout_step(batches: Iterable[Dict], tokenizer, sample: Callable[[torch.Tensor, torch.Tensor, torch.Tensor], torch.Tensor],
-                 feedback: Optional[Callable] = None) -> Dict[str, list]:
+                 feedback: Optional[Callable] = None, num_return_sequences: int = 1) -> Dict[str, list]:
     """`sample(queries, query_attn_masks, images) -> responses [B, response_len]` already cut after EOS / '?' (on the GPU:
-    `generator_sampler(...)` below).  Returns the response dict of online_generator.py:352-362."""
+    `generator_sampler(...)` below).  Returns the response dict of online_generator.py:352-362.
+    num_return_sequences = N > 1 (the reference hard-codes 1): `sample` returns [B * N, response_len], row i * N + j = sample j of query i;
+    every query yields N consecutive records, the query-side columns repeated, and `feedback` sees B * N entries."""
     feedback = feedback or no_feedback
+    N = int(num_return_sequences)
+    if N < 1:
+        raise ValueError(f"num_return_sequences must be >= 1 (got {N})")
+    rep = (lambda xs: list(xs)) if N == 1 else (lambda xs: [x for x in xs for _ in range(N)])
     out: Dict[str, list] = {k: [] for k in ("query", "image_id", "standard_response", "original_generate_response",
                                             "AI_generate_response", "AI_pseudo_response", "AI_json_report", "image_bytes")}
     for batch in batches:
         queries = batch["queries"]
         responses = sample(queries, batch["query_attn_masks"], batch["images"])
+        if responses.shape[0] != N * queries.shape[0]:
+            raise ValueError(f"sample returned {responses.shape[0]} responses for {queries.shape[0]} queries x {N} return sequences")
         text_rsp = decode_batch(tokenizer, responses)
-        text_std = decode_batch(tokenizer, batch["standard_responses"])
+        text_std = rep(decode_batch(tokenizer, batch["standard_responses"]))
         shown = queries.clone()
         shown[shown == IMAGE_TOKEN_INDEX] = tokenizer.bos_token_id
-        text_q = [query_text(q) for q in decode_batch(tokenizer, shown)]
-        fb = feedback(batch["images_url"], text_q, text_rsp, text_std)
+        text_q = rep(query_text(q) for q in decode_batch(tokenizer, shown))
+        fb = feedback(rep(batch["images_url"]), text_q, text_rsp, text_std)
         if not (len(fb["Pseudo_response"]) == len(fb["Generated_response"]) == len(fb["report_json"]) == len(text_rsp)):
             raise ValueError("feedback must return one entry per response")
         out["query"] += ["<image>\n" + q for q in text_q]
-        out["image_id"] += list(batch["images_path"])
+        out["image_id"] += rep(batch["images_path"])
         out["standard_response"] += text_std
         out["original_generate_response"] += text_rsp
         out["AI_generate_response"] += list(fb["Generated_response"])
         out["AI_pseudo_response"] += list(fb["Pseudo_response"])
         out["AI_json_report"] += list(fb["report_json"])
-        out["image_bytes"] += list(batch["images_bytes"])
+        out["image_bytes"] += rep(batch["images_bytes"])
     return out
 
 
 def generator_sampler(generator, *, response_len: int, temperature: float = 1.0, top_k: int = 30, top_p: float = 0.95,
-                      seed: int = 0) -> Callable:
+                      seed: int = 0, num_return_sequences: int = 1) -> Callable:
     """Sampler over the HIP decode path (`generate.Generator.rollout`); a new seed per batch.  Build the generator with
-    `merge_adapter=True` (frozen rollout adapter) or `fuse_swiglu=True` (adapter-free rollout) for the fastest decode step."""
+    `merge_adapter=True` (frozen rollout adapter) or `fuse_swiglu=True` (adapter-free rollout) for the fastest decode step.
+    num_return_sequences = N > 1: N responses per query off one prefill, [B * N, response_len] item-major (pass the same N to `rollout_step`)."""
+    extra = {} if num_return_sequences == 1 else dict(num_return_sequences=int(num_return_sequences))
     state = {"n": 0}
 
     def sample(queries, masks, images):
         state["n"] += 1
         dev = generator.engine.dev
         return generator.rollout(queries.to(dev), masks.to(dev), images.to(dev), response_len=response_len, temperature=temperature,
-                                 top_k=top_k, top_p=top_p, seed=seed + state["n"], additional_stop_ids=QUESTION_MARK_IDS).cpu()
+                                 top_k=top_k, top_p=top_p, seed=seed + state["n"], additional_stop_ids=QUESTION_MARK_IDS, **extra).cpu()
     return sample

@@ -193,6 +193,26 @@ class AutoregressivePolicy(torch.nn.Module):
             batch.row_plan = torch.stack([plan_q.repeat(K), torch.cat(plan_r, 0)], 1).cpu().contiguous()
         return batch
 
+    def respond(self, queries: torch.Tensor, query_attn_masks: torch.Tensor, images: Optional[torch.Tensor] = None,
+                temperature: Optional[float] = None, num_return_sequences: int = 1, *, image_feats: Optional[torch.Tensor] = None,
+                suppress_eos: bool = False, seed: int = 0) -> Dict[str, torch.Tensor]:
+        """Policy.respond / AutoregressivePolicy._respond (rl_models.py:40-57,146-191): generate(do_sample=True, top_k=0, top_p=1.0,
+        temperature, num_return_sequences) with the policy's own adapter, unmerged -> {"responses": [B * n, response_len]}, item-major
+        (row i * n + j = sample j of query i), pad after EOS.  n > 1 draws the n responses of a query off one prefill (context engine).
+        suppress_eos (the reference's args.suppress_eos_at_generation) and the sampler seed are keyword extras.  Generation never records a
+        graph; it is refused while a training forward of a trainable adapter still waits for its backward in grad mode."""
+        if torch.is_grad_enabled() and self.adapter.trainable and self._pending_bwd > 0:
+            raise RuntimeError("respond() between a training forward and its backward: run the backward (or generate under torch.no_grad()) first")
+        from .generate import Generator
+        if temperature is None:
+            temperature = self.temperature
+        extra = {} if int(num_return_sequences) == 1 else dict(num_return_sequences=int(num_return_sequences))
+        with torch.no_grad():
+            gen = Generator(self.engine, self.adapter, merge_adapter=False)
+            responses = gen.generate(queries, query_attn_masks, images, image_feats=image_feats, max_new_tokens=self.response_len,
+                                     temperature=float(temperature), top_k=0, top_p=1.0, seed=int(seed), suppress_eos=bool(suppress_eos), **extra)
+        return dict(responses=responses)
+
     def forward(self, images: Optional[torch.Tensor] = None, queries: torch.Tensor = None,
                 queries_attn_masks: torch.Tensor = None, temperature: Optional[float] = None,
                 image_feats: Optional[torch.Tensor] = None, mode: Optional[str] = None, row_lead: Optional[torch.Tensor] = None,
