@@ -301,6 +301,17 @@ int opadpo_logit_bias_add(float* logits, int ldl, int rows, int V, const int32_t
                           void* stream);
 int opadpo_gather_scores(const float* logits, int ldl, int rows, int V, const int32_t* ids, const int32_t* ids_host, int m, float temperature,
                          int top_k, float top_p, float* scores, void* stream);
+/* Per-token log-prob and entropy of sampled tokens, read from the fp32 logits row the sampler read (any bias added, a suppressed EOS column
+ * -inf).  z = fp32(logits * inv_T), one multiply as in opadpo_head_fwd, inv_T = 1 / temperature; temperature 0 is greedy decoding and reads with
+ * inv_T = 1.  For row b with token tokens[b] (device int32 [rows]):
+ *   logp[b] = z[tok] - logsumexp(z)          ent[b] = logsumexp(z) - sum softmax(z) * z
+ * A column with z = -inf adds 0 to both sums (no NaN).  tokens[b] == pad_id: logp = -0.0, ent = 0 (opadpo_head_fwd's pad rule, by value).
+ * This is the policy's distribution BEFORE the top-k / top-p cuts - what opadpo_seq_logprobs_fwd returns for the same tokens at the same
+ * temperature; with top_k = 0, top_p = 1 it is also the distribution the token was drawn from.  The log-prob under the cut and renormalised
+ * distribution is not computed.  One workgroup per row, the row read once with 16-byte loads.  Any rows >= 1; V % 4 == 0, ldl % 4 == 0, ldl >= V
+ * and a 16-byte aligned logits base, temperature >= 0: refused with text otherwise, nothing launched.  ent is nullable. */
+int opadpo_token_logprobs(const float* logits, int ldl, int rows, int V, const int32_t* tokens, float temperature, int pad_id, float* logp,
+                          float* ent, void* stream);
 
 /* Beam search (HF GenerationMixin._beam_search with do_sample=False, num_return_sequences=1, length_penalty=1.0, early_stopping=False).
  * B items of k beams each; rows = B*k <= 64, 1 <= k <= OPADPO_MAX_BEAMS.  Row i is beam i % k of item i / k.
@@ -528,6 +539,18 @@ int opadpo_decode_begin_n(opadpo_ctx* ctx, int adapter_id, const int32_t* ids, c
  * 64 rows); either refusal clears the setting. */
 int opadpo_ctx_set_logit_processors(opadpo_ctx* ctx, const int32_t* bias_ids, const float* bias, int n, const int32_t* score_ids, int m,
                                     float* scores, int scores_raw);
+/* Per-token log-probs and entropies of the sampled tokens of the NEXT opadpo_decode_begin / opadpo_decode_begin_n of this context.  logp / ent:
+ * caller-owned device fp32 [max_new_tokens, rows], laid out like history (rows = B, or B*n); ent is nullable.  That generation fills both with
+ * the pad values (-0.0 / 0) and then, at every step - the prefill head that yields token 0, every plain step, the captured step under use_graph -
+ * launches opadpo_token_logprobs' kernel right after the sampler on the row it read, with the generation's temperature (a greedy generation,
+ * which the host asks for as temperature 1 / top_k = 1, reads with inv_T = 1) and the device step counter the sampler used.  So slot [t, b] holds
+ * the log-prob of history[t, b] under the policy's distribution before the top-k / top-p cuts (the cut, renormalised distribution is not
+ * computed); a pad token - a finished row, a step never run, a sampled id equal to pad_id - reads -0.0 / 0, and the step on which a row draws EOS
+ * carries EOS's own values.  Any row count the rollout takes (1..256); independent of opadpo_ctx_set_logit_processors (both may be armed; those keep
+ * their 64-row cap).  logp = ent = NULL clears the setting; logp = NULL with ent != NULL is refused.  opadpo_decode_begin reads the setting and
+ * opadpo_decode_end clears it; a generation without it carves the same arena and issues exactly the launches it issued before this entry point
+ * existed.  opadpo_decode_beam_begin refuses an armed context (beam search keeps returning its sequence score), and the refusal clears the setting. */
+int opadpo_ctx_set_output_logprobs(opadpo_ctx* ctx, float* logp, float* ent);
 /* one more token for every row: all launches of a step, asynchronous */
 int opadpo_decode_step(opadpo_ctx* ctx, void* stream);
 /* n_steps more tokens.  use_graph = 0: the launches of every step are issued from the library's own loop (no host work between

@@ -525,6 +525,13 @@ int opadpo_gather_scores(const float* logits, int ldl, int rows, int V, const in
     return bad("opadpo_gather_scores", "need rows <= 64, 0 <= m <= 64, ldl >= V, temperature >= 0, non-null logits / ids / ids_host / scores, ids inside [0, V)");
   return done(e, "opadpo_gather_scores");
 }
+int opadpo_token_logprobs(const float* logits, int ldl, int rows, int V, const int32_t* tokens, float temperature, int pad_id, float* logp,
+                          float* ent, void* stream) {
+  const hipError_t e = launch_token_logprobs(logits, ldl, rows, V, tokens, temperature, pad_id, nullptr, 1, logp, ent, S(stream));
+  if (e == hipErrorInvalidValue)
+    return bad("opadpo_token_logprobs", "need rows >= 1, V % 4 == 0, ldl % 4 == 0, ldl >= V, temperature >= 0, non-null 16-byte aligned logits, non-null tokens / logp");
+  return done(e, "opadpo_token_logprobs");
+}
 
 // ---- gradient exchange for binders that do not go through torch.distributed (opadpo_allreduce_grads) -----------------------
 // The collective library is NOT linked: the entry points resolve ncclAllReduce / ncclReduceScatter / ncclAllGather at first use from whatever RCCL the

@@ -280,6 +280,8 @@ struct opadpo_ctx {
   bool grad_checkpoint = false;                   // opadpo_ctx_set_grad_checkpoint: read by every training forward, remembered in its opadpo_saved
   // opadpo_ctx_set_logit_processors: host copies, read by the next opadpo_decode_begin and cleared by opadpo_decode_end
   struct LogitArm { std::vector<int32_t> bias_ids, score_ids; std::vector<float> bias; float* scores = nullptr; int raw = 0; } next_logit;
+  // opadpo_ctx_set_output_logprobs: caller-owned [max_new_tokens, rows] buffers of the next opadpo_decode_begin (ent nullable), cleared by opadpo_decode_end
+  struct LogprobArm { float *logp = nullptr, *ent = nullptr; } next_lp;
   // dispatch: opadpo_ctx_set_flags(gemm_variant, use_tr), parsed once; the use_tr bits below are off for a negative word
   KernelOverrides kernel;                         // gemm_variant, bits 0, 3 and 8 over the process flags (resolve_flags, per launch)
   bool streaming_dec_gemm = false;                // bit 5: decode steps of 9..64 sequences keep the 8/16-row streaming GEMMs
@@ -308,6 +310,8 @@ struct opadpo_ctx {
     // logit bias of every step and the step-0 scores (opadpo_ctx_set_logit_processors): `logit` = the host copy this generation took, the device tables
     // live in the arena (carved only when armed)
     opadpo_ctx::LogitArm logit; int32_t *bias_ids = nullptr, *score_ids = nullptr; float* bias = nullptr;
+    // per-token log-probs / entropies of the sampled tokens (opadpo_ctx_set_output_logprobs): the buffers this generation took; lp.logp = null: not armed
+    opadpo_ctx::LogprobArm lp;
     // beam decode (opadpo_decode_beam_begin): B = items * beams rows; kc / vc = the items' prefix caches [items, nh, Lp, hd], ks / vs = the
     // rows' suffix caches [B, nh, max_new, hd]; finished = per-item done flags; bs = selection state (decode.hip beam_update_kernel)
     int beams = 0, items = 0; bf16_t *ks = nullptr, *vs = nullptr; BeamState bs{};
@@ -741,6 +745,13 @@ int opadpo_ctx_set_logit_processors(opadpo_ctx* c, const int32_t* bias_ids, cons
   a.bias_ids.assign(bias_ids, bias_ids + n); a.bias.assign(bias, bias + n); a.score_ids.assign(score_ids, score_ids + m);
   a.scores = m > 0 ? scores : nullptr; a.raw = scores_raw;
   c->next_logit = std::move(a);
+  return 0;
+}
+
+int opadpo_ctx_set_output_logprobs(opadpo_ctx* c, float* logp, float* ent) {
+  if (!c) return (int)hipErrorInvalidValue;
+  if (!logp && ent) return cbad(c, __func__, "entropies without log-probs: logp is null and ent is not");
+  c->next_lp.logp = logp; c->next_lp.ent = ent;
   return 0;
 }
 
@@ -1389,6 +1400,8 @@ static hipError_t decode_head(opadpo_ctx* c, const float* src_f32, const float* 
   }
   TRY(launch_sample(D.logits, d.vocab, D.B, d.vocab, D.temperature, D.top_k, D.top_p, D.seed, 0, D.step_d, D.finished, D.pad_id,
                     D.suppress_eos ? -1 : D.eos_id, D.cur_tok, D.history, st));
+  if (D.lp.logp)                      // the row the sampler just read and the token it wrote, at the step it wrote it to (step_d is bumped below)
+    TRY(launch_token_logprobs(D.logits, d.vocab, D.B, d.vocab, D.cur_tok, D.temperature, D.pad_id, D.step_d, D.max_new, D.lp.logp, D.lp.ent, st));
   hipLaunchKernelGGL(add_i32_kernel, dim3(1), dim3(64), 0, st, D.step_d, 1);
   return hipGetLastError();
 }
@@ -1612,6 +1625,13 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
     CKD(hipMemcpyAsync(history, pad.data(), pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     CKD(hipStreamSynchronize(st));
   }
+  // logp / ent [max_new, B] start as the pad values (-0.0 / 0): the steps that never run, when every row finished early
+  if (D.lp.logp) {
+    std::vector<float> neg0((size_t)max_new_tokens * B, -0.0f);
+    CKD(hipMemcpyAsync(D.lp.logp, neg0.data(), neg0.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    if (D.lp.ent) CKD(hipMemsetAsync(D.lp.ent, 0, neg0.size() * sizeof(float), st));
+    CKD(hipStreamSynchronize(st));
+  }
   // token 0 from the prefill logits (beam decode: step 0 of the search on the items' rows)
   if (nret) {
     // the items' last hidden rows expanded to B rows (b.h and, after it is read, D.hs are free here), then the head on B rows as a B-row rollout runs it
@@ -1635,14 +1655,18 @@ int opadpo_decode_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const
   // the setting is for THIS call, accepted or refused; opadpo_decode_end (below, and at the end of the generation) clears what is left of it
   opadpo_ctx::LogitArm arm = std::move(c->next_logit);
   c->next_logit = {};
+  const opadpo_ctx::LogprobArm lp = c->next_lp;          // opadpo_ctx_set_output_logprobs: for THIS call too
+  c->next_lp = {};
   if (B > 256) return cbad(c, __func__, "decode batch above 256 per device is not supported by the decode GEMMs (opadpo_gemm_nt_decode_wide: M <= 256)");
   if (B > 64 && (!arm.bias_ids.empty() || !arm.score_ids.empty()))      // the setting is consumed by the refusal, as by the beam entry point's
     return cbad(c, __func__, "logit bias / first-token scores (opadpo_ctx_set_logit_processors) take at most 64 rows: decode batch above 64 is not supported with them");
   if (!weights_ready(c)) return cbad(c, __func__, "LLM weights not set");
   if (adapter_id < 0 || adapter_id >= OPADPO_MAX_ADAPTERS) return cbad(c, __func__, "adapter id out of range");
   if (!ids || !text_mask || !feats || !history || B <= 0 || Q <= 0 || max_new_tokens <= 0 || temperature <= 0.f) return cbad(c, __func__, "null operand or bad shape");
+  if (lp.logp && c->d.vocab % 4) return cbad(c, __func__, "per-token log-probs (opadpo_ctx_set_output_logprobs) need vocab % 4 == 0 (opadpo_token_logprobs reads 16 bytes at a time)");
   opadpo_decode_end(c);
   c->dec.logit = std::move(arm);
+  c->dec.lp = lp;
   return decode_begin_impl(c, __func__, adapter_id, ids, text_mask, feats, B, Q, 0, 0, max_new_tokens, temperature, top_k, top_p, seed, eos_id, pad_id,
                            suppress_eos, history, (hipStream_t)stream);
 }
@@ -1656,6 +1680,8 @@ int opadpo_decode_begin_n(opadpo_ctx* c, int adapter_id, const int32_t* ids, con
   // the logit-processor setting is for THIS call, accepted or refused (as in opadpo_decode_begin)
   opadpo_ctx::LogitArm arm = std::move(c->next_logit);
   c->next_logit = {};
+  const opadpo_ctx::LogprobArm lp = c->next_lp;          // opadpo_ctx_set_output_logprobs: for THIS call too
+  c->next_lp = {};
   if (n < 1 || n > OPADPO_MAX_RETURN_SEQUENCES) return cbad(c, __func__, "num_return_sequences must be in 1..OPADPO_MAX_RETURN_SEQUENCES (16)");
   if (B > 0 && (long long)B * n > 256)
     return cbad(c, __func__, "B * num_return_sequences above 256 rows per device is not supported by the decode GEMMs (opadpo_gemm_nt_decode_wide: M <= 256)");
@@ -1664,8 +1690,10 @@ int opadpo_decode_begin_n(opadpo_ctx* c, int adapter_id, const int32_t* ids, con
   if (!weights_ready(c)) return cbad(c, __func__, "LLM weights not set");
   if (adapter_id < 0 || adapter_id >= OPADPO_MAX_ADAPTERS) return cbad(c, __func__, "adapter id out of range");
   if (!ids || !text_mask || !feats || !history || B <= 0 || Q <= 0 || max_new_tokens <= 0 || temperature <= 0.f) return cbad(c, __func__, "null operand or bad shape");
+  if (lp.logp && c->d.vocab % 4) return cbad(c, __func__, "per-token log-probs (opadpo_ctx_set_output_logprobs) need vocab % 4 == 0 (opadpo_token_logprobs reads 16 bytes at a time)");
   opadpo_decode_end(c);
   c->dec.logit = std::move(arm);
+  c->dec.lp = lp;
   return decode_begin_impl(c, __func__, adapter_id, ids, text_mask, feats, B, Q, 0, n, max_new_tokens, temperature, top_k, top_p, seed, eos_id, pad_id,
                            suppress_eos, history, (hipStream_t)stream);
 }
@@ -1673,6 +1701,8 @@ int opadpo_decode_begin_n(opadpo_ctx* c, int adapter_id, const int32_t* ids, con
 int opadpo_decode_beam_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats, int B, int Q,
                              int k, int max_new_tokens, int eos_id, int pad_id, void* stream) {
   if (!c) return (int)hipErrorInvalidValue;
+  const bool lp_armed = c->next_lp.logp != nullptr;      // opadpo_ctx_set_output_logprobs: consumed by this call, whichever check refuses it
+  c->next_lp = {};
   if (k < 1 || k > OPADPO_MAX_BEAMS) return cbad(c, __func__, "num_beams must be in 1..OPADPO_MAX_BEAMS (16)");
   if (B <= 0 || B * k > 64) return cbad(c, __func__, "B * num_beams above 64 rows is not supported by the decode GEMMs");
   if (!weights_ready(c)) return cbad(c, __func__, "LLM weights not set");
@@ -1683,6 +1713,7 @@ int opadpo_decode_beam_begin(opadpo_ctx* c, int adapter_id, const int32_t* ids, 
     c->next_logit = {};                            // consumed by the refusal: the generation after it runs without
     return cbad(c, __func__, "logit bias / first-token scores (opadpo_ctx_set_logit_processors) are not supported under beam search");
   }
+  if (lp_armed) return cbad(c, __func__, "per-token log-probs (opadpo_ctx_set_output_logprobs) are not supported under beam search: it returns its sequence score");
   opadpo_decode_end(c);
   return decode_begin_impl(c, __func__, adapter_id, ids, text_mask, feats, B, Q, k, 0, max_new_tokens, 1.0f, 0, 1.0f, 0, eos_id, pad_id, 0, nullptr,
                            (hipStream_t)stream);
@@ -1815,6 +1846,7 @@ int opadpo_decode_end(opadpo_ctx* c) {
   D.beams = 0; D.items = 0; D.nret = 0;
   D.logit = {}; D.bias_ids = nullptr; D.score_ids = nullptr; D.bias = nullptr;
   c->next_logit = {};
+  D.lp = {}; c->next_lp = {};
   return 0;
 }
 

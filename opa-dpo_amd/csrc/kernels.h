@@ -233,6 +233,9 @@ hipError_t launch_logit_bias_add(float* logits, int ldl, int rows, int V, const 
                                  hipStream_t st);
 hipError_t launch_gather_scores(const float* logits, int ldl, int rows, int V, const int32_t* ids, const int32_t* ids_host, int m, float temperature,
                                 int top_k, float top_p, float* scores, hipStream_t st);
+// per-token log-prob / entropy of the sampled tokens (decode.hip: token_logprob_kernel).  step_ptr (nullable): device step counter, outputs [max_steps, rows]
+hipError_t launch_token_logprobs(const float* logits, int ldl, int rows, int V, const int32_t* tokens, float temperature, int pad_id,
+                                 const int32_t* step_ptr, int max_steps, float* logp, float* ent, hipStream_t st);
 hipError_t launch_attn_decode(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, bf16_t* o, const uint8_t* key_mask,
                               int B, int nh, int hd, int ctx, const int32_t* ctx_ptr, int max_ctx, int ldq, float scale,
                               void* workspace, size_t workspace_bytes, hipStream_t st);

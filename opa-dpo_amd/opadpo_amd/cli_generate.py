@@ -42,6 +42,8 @@ def rollout_parser() -> argparse.ArgumentParser:
     ap.add_argument("--top_p", type=float, default=0.95)
     ap.add_argument("--num_return_sequences", type=int, default=1,
                     help="sampled responses per query off one prefill (1..16, per-device batch x N <= 256; the reference hard-codes 1)")
+    ap.add_argument("--output_logprobs", type=_bool, default=False,
+                    help="add each response's summed token log-prob, token count and mean token entropy (before the top-k / top-p cuts) to its record")
     ap.add_argument("--sample_num", type=int, default=0, help="use only the first N rows (0 = all)")
     ap.add_argument("--max_step", type=int, default=0, help="stop after N rollout steps (0 = whole dataset)")
     ap.add_argument("--image_aspect_ratio", default="pad")
@@ -148,7 +150,8 @@ def run_rollout(args, feedback: Optional[Callable] = None, log=print) -> List[st
     ds = QueryResponseDataset(rows, tok, args.query_len, image_size=engine.d.image_size, pad_to_square=args.image_aspect_ratio == "pad", log=log)
     gen = Generator(engine, adapter, merge_adapter=True, fuse_swiglu=True)
     sample = generator_sampler(gen, response_len=args.response_len, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-                               seed=args.seed + 1000 * rank, num_return_sequences=nret)
+                               seed=args.seed + 1000 * rank, num_return_sequences=nret,
+                               **(dict(output_logprobs=True) if bool(getattr(args, "output_logprobs", False)) else {}))
     mine = list(range(rank, len(ds), world))
     per_step = max(args.rollout_per_device_batch_size, args.rollout_batch_size // world)
     files = []

@@ -284,7 +284,7 @@ class CtxEngine(LlavaEngine):
     def generate(self, adapter, queries: torch.Tensor, query_attn_masks: torch.Tensor, image_feats: torch.Tensor, *, max_new_tokens: int,
                  temperature: float, top_k: int, top_p: float, seed: int, eos_token_id: int, pad_token_id: int, suppress_eos: bool,
                  use_graph: bool, logit_bias: Optional[Dict[int, float]] = None, score_ids: Optional[Sequence[int]] = None,
-                 num_return_sequences: int = 1):
+                 num_return_sequences: int = 1, output_logprobs: bool = False):
         """-> responses [B, max_new_tokens] int64 (pad after a row finished); prefill, KV cache and the per-token launch loop (or hipGraph) live in
         the context (opadpo_decode_begin / opadpo_decode_run).
         num_return_sequences = n > 1 (HF generate(do_sample=True, num_return_sequences=n)): n sampled responses per prompt off ONE prefill,
@@ -296,7 +296,13 @@ class CtxEngine(LlavaEngine):
         PROCESSED scores of the first generated token as HF's `generate(output_scores=True).scores[0]` holds them -
         (logit + bias) / temperature, then the top-k / top-p cuts (a cut token reads -inf).
         temperature == 0 means greedy decoding here (HF refuses do_sample=True with temperature 0; this tree's evaluation path treats 0 as
-        greedy and runs it as top_k = 1): the scores are then logit + bias, nothing divided and nothing cut."""
+        greedy and runs it as top_k = 1): the scores are then logit + bias, nothing divided and nothing cut.
+        output_logprobs: the return value gains `logp, ent` ([rows, max_new_tokens] fp32) - (tokens, logp, ent), or (tokens, scores, logp, ent)
+        with score_ids: log-prob of every generated token and entropy of the distribution it came from, read in the decode loop from the
+        logits row the sampler read (opadpo_ctx_set_output_logprobs): bias added, the EOS column -inf under suppress_eos, divided by the
+        temperature (greedy: by 1), BEFORE the top-k / top-p cuts - what AutoregressivePolicy.forward(temperature=T) returns for the same
+        tokens; with top_k = 0, top_p = 1 also the distribution the token was drawn from.  The log-prob under the cut, renormalised
+        distribution is not computed.  A pad token (a finished row, a sampled id equal to pad) reads -0.0 / 0, the trainer's convention."""
         dev, d = self.dev, self.d
         B, Q = queries.shape
         nret = int(num_return_sequences)
@@ -327,6 +333,11 @@ class CtxEngine(LlavaEngine):
                        (C.c_int32 * m)(*(sids or ())), m, _ptr(scores), int(greedy))
         elif sids is not None:
             scores = torch.empty(rows, 0, dtype=torch.float32, device=dev)
+        lp = ent = None
+        if output_logprobs:
+            lp = torch.empty(max_new_tokens, rows, dtype=torch.float32, device=dev)
+            ent = torch.empty(max_new_tokens, rows, dtype=torch.float32, device=dev)
+            self._call("opadpo_ctx_set_output_logprobs", _ptr(lp), _ptr(ent))
         try:
             if nret == 1:
                 self._call("opadpo_decode_begin", slot, _ptr(ids), _ptr(tmask), _ptr(feats), B, Q, int(max_new_tokens), float(temperature), int(top_k),
@@ -348,7 +359,10 @@ class CtxEngine(LlavaEngine):
         finally:
             self._call("opadpo_decode_end")
         tokens = history.t().contiguous().to(torch.int64)
-        return tokens if score_ids is None else (tokens, scores)
+        out = (tokens,) if score_ids is None else (tokens, scores)
+        if output_logprobs:
+            out += (lp.t().contiguous(), ent.t().contiguous())
+        return out[0] if len(out) == 1 else out
 
     @torch.no_grad()
     def generate_beams(self, adapter, queries: torch.Tensor, query_attn_masks: torch.Tensor, image_feats: torch.Tensor, *, num_beams: int,

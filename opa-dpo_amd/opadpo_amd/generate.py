@@ -74,15 +74,24 @@ class Generator:
                  image_feats: Optional[torch.Tensor] = None, max_new_tokens: int, temperature: float = 1.0, top_k: int = 0,
                  top_p: float = 1.0, seed: int = 0, eos_token_id: int = EOS_ID, pad_token_id: int = PAD_ID,
                  suppress_eos: bool = False, num_beams: int = 1, logit_bias: Optional[Dict[int, float]] = None,
-                 score_ids: Optional[Sequence[int]] = None, num_return_sequences: int = 1):
+                 score_ids: Optional[Sequence[int]] = None, num_return_sequences: int = 1, output_logprobs: bool = False):
         """-> responses [B, max_new_tokens] int64 (pad after a row finished).  num_beams > 1: beam search (HF num_beams, do_sample=False;
         temperature / top_k / top_p / seed are not used), the best hypothesis per query.
         num_return_sequences = n > 1 (context engine only; ctx.CtxEngine.generate documents it): n sampled responses per prompt off one prefill,
         responses [B * n, max_new_tokens], row i * n + j = sample j of prompt i.
         logit_bias / score_ids (context engine only; ctx.CtxEngine.generate documents them): an additive bias on single tokens' logits at every
-        step, and the first generated token's processed scores at score_ids - the return value is then (responses, scores [B, m])."""
+        step, and the first generated token's processed scores at score_ids - the return value is then (responses, scores [B, m]).
+        output_logprobs (context engine only; ctx.CtxEngine.generate documents it): the return value gains `logp, ent` [rows, max_new_tokens] fp32,
+        the per-token log-probs and entropies of the generated tokens before the top-k / top-p cuts; not under beam search."""
         eng, d, b = self.engine, self.engine.d, self.engine.base
         dev = eng.dev
+        if output_logprobs:
+            if not hasattr(eng, "ctx"):
+                raise NotImplementedError("output_logprobs runs on the context engine (CtxEngine) only: the op-level LlavaEngine loop is a cross-check "
+                                          "of the sampling rollout")
+            if num_beams > 1:
+                raise NotImplementedError("output_logprobs is not supported under beam search (it keeps returning its sequence score); the context "
+                                          "engine reads per-token log-probs in the sampling / greedy rollout (num_beams = 1)")
         if logit_bias or score_ids is not None:
             if not hasattr(eng, "ctx"):
                 raise NotImplementedError("logit_bias / score_ids run on the context engine (CtxEngine) only: the sampler of the op-level LlavaEngine "
@@ -106,6 +115,8 @@ class Generator:
             extra = {} if not logit_bias and score_ids is None else dict(logit_bias=logit_bias, score_ids=score_ids)
             if num_return_sequences != 1:
                 extra["num_return_sequences"] = int(num_return_sequences)
+            if output_logprobs:
+                extra["output_logprobs"] = True
             if num_beams > 1:
                 return eng.generate_beams(self.adapter, queries, query_attn_masks, image_feats, num_beams=num_beams, max_new_tokens=max_new_tokens,
                                           eos_token_id=eos_token_id, pad_token_id=pad_token_id, use_graph=self.use_graph)[0]
@@ -235,10 +246,19 @@ class Generator:
         return history.t().contiguous().to(torch.int64)
 
     def rollout(self, queries, query_attn_masks, images, *, response_len: int, temperature: float = 1.0, top_k: int = 30,
-                top_p: float = 0.95, seed: int = 0, additional_stop_ids: Sequence[int] = (1577, 29973), num_return_sequences: int = 1) -> torch.Tensor:
+                top_p: float = 0.95, seed: int = 0, additional_stop_ids: Sequence[int] = (1577, 29973), num_return_sequences: int = 1,
+                output_logprobs: bool = False):
         """Online_Generator.rollout's tensor part (online_generator.py:292-323): sample, then cut at EOS / '?'.  num_return_sequences = n > 1:
-        [B * n, response_len], row i * n + j = sample j of query i."""
+        [B * n, response_len], row i * n + j = sample j of query i.
+        output_logprobs: -> (responses, logp, ent), the per-token log-probs / entropies of `generate` with every position whose token is pad AFTER
+        the cut set to -0.0 / 0 (the values of the tokens the cut removed do not belong to the response)."""
         extra = {} if num_return_sequences == 1 else dict(num_return_sequences=int(num_return_sequences))
-        resp = self.generate(queries, query_attn_masks, images, max_new_tokens=response_len, temperature=temperature,
-                             top_k=top_k, top_p=top_p, seed=seed, **extra)
-        return truncate_after_eos_with_padding(resp, EOS_ID, PAD_ID, list(additional_stop_ids))
+        if not output_logprobs:
+            resp = self.generate(queries, query_attn_masks, images, max_new_tokens=response_len, temperature=temperature,
+                                 top_k=top_k, top_p=top_p, seed=seed, **extra)
+            return truncate_after_eos_with_padding(resp, EOS_ID, PAD_ID, list(additional_stop_ids))
+        resp, logp, ent = self.generate(queries, query_attn_masks, images, max_new_tokens=response_len, temperature=temperature,
+                                        top_k=top_k, top_p=top_p, seed=seed, output_logprobs=True, **extra)
+        resp = truncate_after_eos_with_padding(resp, EOS_ID, PAD_ID, list(additional_stop_ids))
+        pad = resp == PAD_ID
+        return resp, logp.masked_fill(pad, -0.0), ent.masked_fill(pad, 0.0)

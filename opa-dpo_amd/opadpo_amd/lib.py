@@ -72,6 +72,7 @@ SIGNATURES = {
     "opadpo_sample": [_p, _i, _i, _i, _f, _i, _f, _u64, _u64, _p, _p, _i, _i, _p, _p, _p],
     "opadpo_logit_bias_add": [_p, _i, _i, _i, _p, _p, _p, _i, _p],
     "opadpo_gather_scores": [_p, _i, _i, _i, _p, _p, _i, _f, _i, _f, _p, _p],
+    "opadpo_token_logprobs": [_p, _i, _i, _i, _p, _f, _i, _p, _p, _p],
     "opadpo_attn_decode_beam": [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _f, _p, _sz, _p],
     "opadpo_attn_decode_shared": [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _f, _p, _sz, _i, _p],
     "opadpo_beam_step": [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
@@ -97,6 +98,7 @@ SIGNATURES.update({
     "opadpo_saved_release": [_p, _p],
     "opadpo_saved_residual": [_p, _p, _i, _p, _p, _p],
     "opadpo_ctx_set_logit_processors": [_p, _p, _p, _i, _p, _i, _p, _i],
+    "opadpo_ctx_set_output_logprobs": [_p, _p, _p],
     "opadpo_decode_begin": [_p, _i, _p, _p, _p, _i, _i, _i, _f, _i, _f, _u64, _i, _i, _i, _p, _p],
     "opadpo_decode_begin_n": [_p, _i, _p, _p, _p, _i, _i, _i, _i, _f, _i, _f, _u64, _i, _i, _i, _p, _p],
     "opadpo_decode_step": [_p, _p],

@@ -19,6 +19,7 @@ from .rollout_data import IMAGE_TOKEN_INDEX
 
 QUESTION_MARK_IDS = (1577, 29973)          # '?' alone and after a newline in the Llama vocabulary (online_generator.py:311-315)
 QUERY_HEAD, QUERY_TAIL = "USER:  \n", " ASSISTANT:"
+LOGPROB_COLUMNS = ("original_generate_response_logprob", "original_generate_response_tokens", "original_generate_response_entropy")
 
 
 def no_feedback(images_url: Sequence[str], queries: Sequence[str], responses: Sequence[str], standard: Sequence[str]) -> Dict[str, list]:
@@ -40,7 +41,11 @@ def rollout_step(batches: Iterable[Dict], tokenizer, sample: Callable[[torch.Ten
     """`sample(queries, query_attn_masks, images) -> responses [B, response_len]` already cut after EOS / '?' (on the GPU:
     `generator_sampler(...)` below).  Returns the response dict of online_generator.py:352-362.
     num_return_sequences = N > 1 (the reference hard-codes 1): `sample` returns [B * N, response_len], row i * N + j = sample j of query i;
-    every query yields N consecutive records, the query-side columns repeated, and `feedback` sees B * N entries."""
+    every query yields N consecutive records, the query-side columns repeated, and `feedback` sees B * N entries.
+    A `sample` that returns `(responses, logp, ent)` (`generator_sampler(..., output_logprobs=True)`; logp / ent fp32 of the responses' shape)
+    adds three columns per record, taken over the response's non-pad tokens: `original_generate_response_logprob` (sum of the token
+    log-probs), `original_generate_response_tokens` (their count) and `original_generate_response_entropy` (mean token entropy, 0.0 for an
+    empty response).  Every batch of a step must then return the triple."""
     feedback = feedback or no_feedback
     N = int(num_return_sequences)
     if N < 1:
@@ -48,11 +53,33 @@ def rollout_step(batches: Iterable[Dict], tokenizer, sample: Callable[[torch.Ten
     rep = (lambda xs: list(xs)) if N == 1 else (lambda xs: [x for x in xs for _ in range(N)])
     out: Dict[str, list] = {k: [] for k in ("query", "image_id", "standard_response", "original_generate_response",
                                             "AI_generate_response", "AI_pseudo_response", "AI_json_report", "image_bytes")}
+    with_lp: Optional[bool] = None
     for batch in batches:
         queries = batch["queries"]
         responses = sample(queries, batch["query_attn_masks"], batch["images"])
+        triple = isinstance(responses, (tuple, list))
+        if with_lp is None:
+            with_lp = triple
+            if triple:
+                out.update({k: [] for k in LOGPROB_COLUMNS})
+        elif with_lp != triple:
+            raise ValueError("sample must return responses or (responses, logp, ent) for every batch of a step, not a mix")
+        if triple:
+            if len(responses) != 3:
+                raise ValueError(f"sample returned {len(responses)} values: expected responses or (responses, logp, ent)")
+            responses, logp, ent = responses
+            if tuple(logp.shape) != tuple(responses.shape) or tuple(ent.shape) != tuple(responses.shape):
+                raise ValueError(f"sample returned logp {tuple(logp.shape)} / ent {tuple(ent.shape)} for responses {tuple(responses.shape)}")
         if responses.shape[0] != N * queries.shape[0]:
             raise ValueError(f"sample returned {responses.shape[0]} responses for {queries.shape[0]} queries x {N} return sequences")
+        if triple:
+            keep = (responses != tokenizer.pad_token_id).cpu()
+            count = keep.sum(dim=1)
+            lp_sum = (logp.detach().cpu().double() * keep).sum(dim=1)
+            ent_sum = (ent.detach().cpu().double() * keep).sum(dim=1)
+            out["original_generate_response_logprob"] += [float(v) for v in lp_sum]
+            out["original_generate_response_tokens"] += [int(v) for v in count]
+            out["original_generate_response_entropy"] += [float(s) / int(c) if int(c) else 0.0 for s, c in zip(ent_sum, count)]
         text_rsp = decode_batch(tokenizer, responses)
         text_std = rep(decode_batch(tokenizer, batch["standard_responses"]))
         shown = queries.clone()
@@ -73,16 +100,21 @@ def rollout_step(batches: Iterable[Dict], tokenizer, sample: Callable[[torch.Ten
 
 
 def generator_sampler(generator, *, response_len: int, temperature: float = 1.0, top_k: int = 30, top_p: float = 0.95,
-                      seed: int = 0, num_return_sequences: int = 1) -> Callable:
+                      seed: int = 0, num_return_sequences: int = 1, output_logprobs: bool = False) -> Callable:
     """Sampler over the HIP decode path (`generate.Generator.rollout`); a new seed per batch.  Build the generator with
     `merge_adapter=True` (frozen rollout adapter) or `fuse_swiglu=True` (adapter-free rollout) for the fastest decode step.
-    num_return_sequences = N > 1: N responses per query off one prefill, [B * N, response_len] item-major (pass the same N to `rollout_step`)."""
+    num_return_sequences = N > 1: N responses per query off one prefill, [B * N, response_len] item-major (pass the same N to `rollout_step`).
+    output_logprobs: the sampler returns (responses, logp, ent) - `Generator.rollout(..., output_logprobs=True)` - and `rollout_step` adds
+    the per-response log-prob / token count / mean entropy columns."""
     extra = {} if num_return_sequences == 1 else dict(num_return_sequences=int(num_return_sequences))
+    if output_logprobs:
+        extra["output_logprobs"] = True
     state = {"n": 0}
 
     def sample(queries, masks, images):
         state["n"] += 1
         dev = generator.engine.dev
-        return generator.rollout(queries.to(dev), masks.to(dev), images.to(dev), response_len=response_len, temperature=temperature,
-                                 top_k=top_k, top_p=top_p, seed=seed + state["n"], additional_stop_ids=QUESTION_MARK_IDS, **extra).cpu()
+        got = generator.rollout(queries.to(dev), masks.to(dev), images.to(dev), response_len=response_len, temperature=temperature,
+                                top_k=top_k, top_p=top_p, seed=seed + state["n"], additional_stop_ids=QUESTION_MARK_IDS, **extra)
+        return tuple(t.cpu() for t in got) if output_logprobs else got.cpu()
     return sample

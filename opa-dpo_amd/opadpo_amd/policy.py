@@ -195,10 +195,12 @@ class AutoregressivePolicy(torch.nn.Module):
 
     def respond(self, queries: torch.Tensor, query_attn_masks: torch.Tensor, images: Optional[torch.Tensor] = None,
                 temperature: Optional[float] = None, num_return_sequences: int = 1, *, image_feats: Optional[torch.Tensor] = None,
-                suppress_eos: bool = False, seed: int = 0) -> Dict[str, torch.Tensor]:
+                suppress_eos: bool = False, seed: int = 0, output_logprobs: bool = False) -> Dict[str, torch.Tensor]:
         """Policy.respond / AutoregressivePolicy._respond (rl_models.py:40-57,146-191): generate(do_sample=True, top_k=0, top_p=1.0,
         temperature, num_return_sequences) with the policy's own adapter, unmerged -> {"responses": [B * n, response_len]}, item-major
         (row i * n + j = sample j of query i), pad after EOS.  n > 1 draws the n responses of a query off one prefill (context engine).
+        output_logprobs: the result gains "responses_logprobs" / "responses_entropies" [B * n, response_len] fp32, read in the decode loop at the
+        policy's temperature (CtxEngine.generate): with top_k = 0, top_p = 1 they are the behaviour policy's own values, pad positions -0.0 / 0.
         suppress_eos (the reference's args.suppress_eos_at_generation) and the sampler seed are keyword extras.  Generation never records a
         graph; it is refused while a training forward of a trainable adapter still waits for its backward in grad mode."""
         if torch.is_grad_enabled() and self.adapter.trainable and self._pending_bwd > 0:
@@ -207,10 +209,15 @@ class AutoregressivePolicy(torch.nn.Module):
         if temperature is None:
             temperature = self.temperature
         extra = {} if int(num_return_sequences) == 1 else dict(num_return_sequences=int(num_return_sequences))
+        if output_logprobs:
+            extra["output_logprobs"] = True
         with torch.no_grad():
             gen = Generator(self.engine, self.adapter, merge_adapter=False)
             responses = gen.generate(queries, query_attn_masks, images, image_feats=image_feats, max_new_tokens=self.response_len,
                                      temperature=float(temperature), top_k=0, top_p=1.0, seed=int(seed), suppress_eos=bool(suppress_eos), **extra)
+        if output_logprobs:
+            responses, logp, ent = responses
+            return dict(responses=responses, responses_logprobs=logp, responses_entropies=ent)
         return dict(responses=responses)
 
     def forward(self, images: Optional[torch.Tensor] = None, queries: torch.Tensor = None,
