@@ -281,6 +281,16 @@ int opadpo_rope_kv_append(uint16_t* qkv, int ld, const float* cos_tab, const flo
 int opadpo_attn_decode_fused(const uint16_t* qkv, int ld, const float* cos_tab, const float* sin_tab, uint16_t* k_cache, uint16_t* v_cache,
                              uint16_t* o, const uint8_t* key_mask, int B, int nh, int hd, const int32_t* pos_ptr, int max_ctx, float scale,
                              void* workspace, size_t workspace_bytes, void* stream);
+/* opadpo_attn_decode_fused with a position PER ROW (continuous rollout: the rows of a launch sit at different context lengths): pos_rows [B]
+ * device int32, row b is rotated at pos_rows[b], appends its k / v at [b, h, pos_rows[b], :] and attends keys 0..pos_rows[b].  The key-range
+ * split (a function of B, nh and max_ctx alone), the workgroup shape and the range that appends are those of opadpo_attn_decode_fused, so row
+ * b's output and the k / v it appends are bit-identical to row b of opadpo_attn_decode_fused run with every row at pos_rows[b] on the same
+ * caches, B and max_ctx.  A position outside [0, max_ctx - 1] is clamped into it: no row reads or writes outside its own cache rows, key-mask
+ * row or the first max_ctx rows of the RoPE tables.  Cache slots behind a row's position are never read.  Refused with text, nothing launched:
+ * a null operand (key_mask and workspace are nullable as above), head_dim other than 64 / 128, a misaligned leading dimension. */
+int opadpo_attn_decode_fused_rows(const uint16_t* qkv, int ld, const float* cos_tab, const float* sin_tab, uint16_t* k_cache, uint16_t* v_cache,
+                                  uint16_t* o, const uint8_t* key_mask, int B, int nh, int hd, const int32_t* pos_rows, int max_ctx, float scale,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 /* temperature -> top-k -> top-p -> multinomial (HF logits processors order); one draw per row from
  * a counter-based generator keyed on (seed, step, row).  finished rows emit pad_id; a row that draws eos_id (>= 0) is
  * marked finished.  step_ptr (device int32, nullable) overrides `step`; history (nullable) [steps, rows] receives the
@@ -288,6 +298,16 @@ int opadpo_attn_decode_fused(const uint16_t* qkv, int ld, const float* cos_tab, 
 int opadpo_sample(const float* logits, int ldl, int rows, int V, float temperature, int top_k, float top_p,
                   uint64_t seed, uint64_t step, const int32_t* step_ptr, uint8_t* finished, int pad_id, int eos_id,
                   int32_t* out, int32_t* history, void* stream);
+/* opadpo_sample with a seed, a step and a cap PER ROW (continuous rollout; device arrays [rows]: seed_rows uint64, step_rows / cap_rows int32).
+ * Row b draws the token opadpo_sample draws for it with scalar (seed_rows[b], step_rows[b]) on the same logits - the draw stays
+ * f(seed, step, row) - writes it to out[b] and to history[b, step_rows[b]] (history [rows, max_steps] int32, ROW-major: a row's tokens are
+ * contiguous; nullable), and then advances step_rows[b] by one.  The row is marked finished when it drew eos_id (>= 0) or when the token was its
+ * cap_rows[b]-th (its step reached cap_rows[b]).  A finished row - and a row whose step is outside [0, min(cap_rows[b], max_steps)) - writes
+ * pad_id to out[b] and nothing else: its step does not advance and no history slot is touched, however many launches it sits through.
+ * `finished` is required.  Both sampler kernels (the row in LDS for V % 4 == 0 and V <= 32768, the generic one otherwise) have this form. */
+int opadpo_sample_rows(const float* logits, int ldl, int rows, int V, float temperature, int top_k, float top_p, const uint64_t* seed_rows,
+                       int32_t* step_rows, const int32_t* cap_rows, int max_steps, uint8_t* finished, int pad_id, int eos_id, int32_t* out,
+                       int32_t* history, void* stream);
 /* Logits processors of the yes/no evaluation generator (eval_llava_rlhf_coco/model_vqa_logit.py), for rows <= 64 and at most
  * OPADPO_MAX_LOGIT_IDS table entries.  ids (int32) / bias (fp32) are DEVICE arrays; ids_host is the host copy of ids, checked before anything is
  * launched: every id in [0, V), and no id twice in a bias table.
@@ -560,6 +580,35 @@ int opadpo_decode_run(opadpo_ctx* ctx, int n_steps, int use_graph, void* stream)
 /* synchronous: *all_finished = every row has emitted EOS (beam decode: every item is done) */
 int opadpo_decode_all_finished(opadpo_ctx* ctx, int* all_finished, void* stream);
 int opadpo_decode_end(opadpo_ctx* ctx);
+/* Continuous batching for the sampling rollout: a session of `slots` decode rows that are REFILLED as they finish, instead of a batch that runs
+ * until its longest row is done.  Every slot has its own position, step, cap (the most tokens its prompt may generate, <= max_new_tokens), seed
+ * and KV cache [Q+575+max_new_tokens]; the step's kernels read them per row (opadpo_attn_decode_fused_rows, opadpo_sample_rows, the per-row form
+ * of opadpo_token_logprobs' kernel), everything else of a step is opadpo_decode_begin's step on `slots` rows - the same GEMM paths by row count and
+ * adapter kind.  A slot finishes when it draws EOS or has written its cap-th token; a finished or never used slot sits through further steps
+ * without moving: it emits pad, its position and step stay, and it touches no memory outside its own cache, key-mask, history and log-prob rows.
+ * The prompt in slot s draws with (its seed, its own step, s): its tokens are those of row s of an opadpo_decode_begin batch of `slots` rows with
+ * that prompt at row s, that seed and the same max_new_tokens, up to its cap.
+ *   opadpo_decode_cont_begin   carves the arena of `slots` rows; every slot starts idle (finished).  1 <= slots <= 256.
+ *   opadpo_decode_cont_admit   n prompts into n finished slots: slot_ids / seeds / caps are HOST arrays [n], ids [n, Q] / text_mask [n, Q] /
+ *                              feats [n, 576, hidden] device arrays in the order of slot_ids.  Prompts whose slots are consecutive share a prefill
+ *                              pass (at most 64 per pass); K / V land in the slots' caches, the slots' key-mask rows are rewritten, position Lp-1,
+ *                              step 0, cap and seed are set, the history / log-prob rows become pad / -0.0 / 0, and token 0 is sampled for the
+ *                              admitted slots only.  The prefill scratch is allocated and released inside the call; synchronises once.
+ *   opadpo_decode_run / _step  step every slot (a step captured under use_graph = 1 stays valid across admissions: its pointers are the arena's).
+ *   opadpo_decode_cont_poll    synchronous: finished_host [slots] (host) = the slots' finished flags; the session remembers them.
+ *   opadpo_decode_cont_retire  asynchronous device copies of a finished slot's history row into tokens [max_new_tokens] int32 and, when the
+ *                              session was armed, of its log-prob / entropy rows into logp / ent [max_new_tokens] fp32 (both nullable).
+ *   opadpo_decode_end          ends the session.
+ * opadpo_ctx_set_output_logprobs arms a session as it arms a generation; its buffers are then [slots, max_new_tokens], slot-major like the
+ * session's history.  Refused with text before anything is launched (the begin's refusals disarm, as opadpo_decode_begin's do): slots outside
+ * 1..256; armed logit processors (they keep the static rollout); a cap outside 1..max_new_tokens; a slot id outside 0..slots-1 or repeated in one
+ * call; admission into, or retirement of, a slot that was not finished at the last poll (a slot is finished from begin until it is admitted). */
+int opadpo_decode_cont_begin(opadpo_ctx* ctx, int adapter_id, int slots, int Q, int max_new_tokens, float temperature, int top_k, float top_p,
+                             int eos_id, int pad_id, int suppress_eos, void* stream);
+int opadpo_decode_cont_admit(opadpo_ctx* ctx, int n, const int32_t* slot_ids, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats,
+                             const uint64_t* seeds, const int32_t* caps, void* stream);
+int opadpo_decode_cont_poll(opadpo_ctx* ctx, uint8_t* finished_host, void* stream);
+int opadpo_decode_cont_retire(opadpo_ctx* ctx, int slot, int32_t* tokens, float* logp, float* ent, void* stream);
 /* model.generate(num_beams=k, do_sample=False) (eval_llava_rlhf_coco/model_vqa.py): ONE prefill of the B questions (its KV cache is the
  * items' shared prefix), the k beams' generated keys in per-row suffix caches addressed by a slot table, and step 0 from the prefill logits.
  * opadpo_decode_step / _run / _all_finished / _end then work on the beam decode (B*k rows; selection on the device, nothing read back).

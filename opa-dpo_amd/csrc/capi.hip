@@ -452,6 +452,18 @@ int opadpo_attn_decode_fused(const uint16_t* qkv, int ld, const float* cos_tab, 
                                        workspace, workspace_bytes, S(stream)),
               "opadpo_attn_decode_fused");
 }
+int opadpo_attn_decode_fused_rows(const uint16_t* qkv, int ld, const float* cos_tab, const float* sin_tab, uint16_t* k_cache, uint16_t* v_cache,
+                                  uint16_t* o, const uint8_t* key_mask, int B, int nh, int hd, const int32_t* pos_rows, int max_ctx, float scale,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "opadpo_attn_decode_fused_rows";
+  if (!qkv || !cos_tab || !sin_tab || !k_cache || !v_cache || !o || !pos_rows) return bad(fn, "null operand (pos_rows [B] is required)");
+  if (B <= 0 || nh <= 0 || max_ctx < 1) return bad(fn, "bad shape: need B >= 1, nh >= 1, max_ctx >= 1");
+  if (hd != 64 && hd != 128) return bad(fn, "head_dim must be 64 or 128");
+  if (ld % 8 || ld < 3 * nh * hd) return bad(fn, "qkv rows must hold [q|k|v] with an aligned leading dimension");
+  return done(launch_attn_decode_fused_rows(qkv, ld, cos_tab, sin_tab, k_cache, v_cache, o, key_mask, B, nh, hd, pos_rows, max_ctx, scale, workspace,
+                                            workspace_bytes, S(stream)),
+              fn);
+}
 int opadpo_attn_decode_beam(const uint16_t* qkv, int ld, const float* cos_tab, const float* sin_tab, const uint16_t* k_prefix,
                             const uint16_t* v_prefix, uint16_t* k_suffix, uint16_t* v_suffix, uint16_t* o, const uint8_t* prefix_mask, int B, int k,
                             int nh, int hd, const int32_t* pos_ptr, int Lp, int max_new, const int32_t* table, float scale, void* workspace,
@@ -509,6 +521,17 @@ int opadpo_sample(const float* logits, int ldl, int rows, int V, float temperatu
   return done(launch_sample(logits, ldl, rows, V, temperature, top_k, top_p, seed, step, step_ptr, finished, pad_id, eos_id, out,
                             history, S(stream)),
               "opadpo_sample");
+}
+int opadpo_sample_rows(const float* logits, int ldl, int rows, int V, float temperature, int top_k, float top_p, const uint64_t* seed_rows,
+                       int32_t* step_rows, const int32_t* cap_rows, int max_steps, uint8_t* finished, int pad_id, int eos_id, int32_t* out,
+                       int32_t* history, void* stream) {
+  const char* fn = "opadpo_sample_rows";
+  if (!(temperature > 0.f)) return bad(fn, "temperature must be > 0");
+  if (rows < 1 || V < 1 || ldl < V || max_steps < 1) return bad(fn, "bad shape: need rows >= 1, V >= 1, ldl >= V, max_steps >= 1");
+  if (!logits || !seed_rows || !step_rows || !cap_rows || !finished || !out) return bad(fn, "null operand (only history is nullable)");
+  return done(launch_sample_rows(logits, ldl, rows, V, temperature, top_k, top_p, seed_rows, step_rows, cap_rows, max_steps, nullptr, 0, finished, pad_id,
+                                 eos_id, out, history, S(stream)),
+              fn);
 }
 // the launch wrappers refuse (hipErrorInvalidValue, nothing launched) what the message lists; the text is written here, where the caller reads it
 int opadpo_logit_bias_add(float* logits, int ldl, int rows, int V, const int32_t* ids, const float* bias, const int32_t* ids_host, int n,

@@ -318,6 +318,11 @@ struct opadpo_ctx {
     // n sampled responses per prompt (opadpo_decode_begin_n, nret >= 2): B = items * nret rows on the beam decode's cache layout (kc / vc per item,
     // ks / vs per row, key_mask [items, Lp]); everything else is the sampling rollout of B rows
     int nret = 0;
+    // continuous rollout (opadpo_decode_cont_begin): B = slots, every slot with its own position / step / cap / seed; hist_rows [slots, max_new] lives
+    // in the arena (lp.logp / lp.ent, when armed, have that layout too); slot_free = the host's view of the finished flags: all set at begin, cleared by
+    // an admission, refreshed by opadpo_decode_cont_poll - an admission or a retirement is checked against it before anything is launched
+    bool cont = false; int Q = 0; int32_t *pos_rows = nullptr, *step_rows = nullptr, *cap_rows = nullptr, *hist_rows = nullptr; uint64_t* seed_rows = nullptr;
+    std::vector<uint8_t> slot_free;
     hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; hipStream_t cap_stream = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;
   } dec;
 };
@@ -1379,7 +1384,9 @@ static hipError_t decode_gemm(opadpo_ctx* c, const GemmNTArgs& g, int mode, int 
   return g.M > 64 ? launch_gemm_nt_decw(g, mode, splits, ctx_flags(c), st) : launch_gemm_nt_dec64(g, mode, splits, ctx_flags(c), st);
 }
 // rows = D.B, or the items of a beam decode for its step 0 (the prefill's last rows; every beam of an item reads the item's logits row)
-static hipError_t decode_head(opadpo_ctx* c, const float* src_f32, const float* partials, int n_partials, hipStream_t st, int rows = -1) {
+// continuous rollout: ids / n_ids = the admitted slots (device array) whose token 0 an admission samples; a step samples every slot (n_ids = 0)
+static hipError_t decode_head(opadpo_ctx* c, const float* src_f32, const float* partials, int n_partials, hipStream_t st, int rows = -1,
+                              const int32_t* ids = nullptr, int n_ids = 0) {
   opadpo_ctx::Decode& D = c->dec;
   const opadpo_dims& d = c->d;
   if (rows < 0) rows = D.B;
@@ -1397,6 +1404,14 @@ static hipError_t decode_head(opadpo_ctx* c, const float* src_f32, const float* 
   if (D.suppress_eos) {
     hipLaunchKernelGGL(set_column_f32_kernel, g1(D.B), dim3(256), 0, st, D.logits, d.vocab, D.B, D.eos_id, -INFINITY);
     TRY(hipGetLastError());
+  }
+  if (D.cont) {                       // a step and a seed per slot; the sampler advances the slot's step itself, so the log-prob kernel reads step - 1
+    TRY(launch_sample_rows(D.logits, d.vocab, D.B, d.vocab, D.temperature, D.top_k, D.top_p, D.seed_rows, D.step_rows, D.cap_rows, D.max_new, ids, n_ids,
+                           D.finished, D.pad_id, D.suppress_eos ? -1 : D.eos_id, D.cur_tok, D.hist_rows, st));
+    if (D.lp.logp)
+      TRY(launch_token_logprobs_rows(D.logits, d.vocab, D.B, d.vocab, D.cur_tok, D.temperature, D.pad_id, D.step_rows, D.max_new, ids, n_ids, D.lp.logp,
+                                     D.lp.ent, st));
+    return hipSuccess;
   }
   TRY(launch_sample(D.logits, d.vocab, D.B, d.vocab, D.temperature, D.top_k, D.top_p, D.seed, 0, D.step_d, D.finished, D.pad_id,
                     D.suppress_eos ? -1 : D.eos_id, D.cur_tok, D.history, st));
@@ -1427,11 +1442,17 @@ static hipError_t decode_one(opadpo_ctx* c, hipStream_t st) {
                                        D.items, D.nret, nh, hd, D.pos_d, D.Lp, D.max_new, scale, D.ws, D.ws_bytes, c->shared_attn_per_row ? 1 : 0, st);
     }
     const size_t per_layer = (size_t)B * nh * D.max_ctx * hd;
+    if (D.cont)
+      return launch_attn_decode_fused_rows(b.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * per_layer, D.vc + i * per_layer, b.attn, D.key_mask, B, nh, hd,
+                                           D.pos_rows, D.max_ctx, scale, D.ws, D.ws_bytes, st);
     return launch_attn_decode_fused(b.qkv, 3 * H, c->cosb, c->sinb, D.kc + i * per_layer, D.vc + i * per_layer, b.attn, D.key_mask, B, nh, hd, D.pos_d,
                                     D.max_ctx, scale, D.ws, D.ws_bytes, st);
   };
-  hipLaunchKernelGGL(add_i32_kernel, dim3(1), dim3(64), 0, st, D.pos_d, 1);
-  TRY(hipGetLastError());
+  if (D.cont) TRY(launch_decode_rows_advance(D.pos_rows, D.finished, B, D.max_ctx, st));      // live slots move on, finished ones stay
+  else {
+    hipLaunchKernelGGL(add_i32_kernel, dim3(1), dim3(64), 0, st, D.pos_d, 1);
+    TRY(hipGetLastError());
+  }
   TRY(launch_gather_rows(c->embed, H, D.cur_tok, D.emb, B, H, st));
   if (D.use64) {
     // 9..256 tokens: the decode GEMMs (opadpo_gemm_nt_decode up to 64 tokens, opadpo_gemm_nt_decode_wide above); x / b.h = fp32 residual stream, part_o / part_d = K-slice partial tiles of the o / down
@@ -1480,6 +1501,50 @@ static hipError_t decode_one(opadpo_ctx* c, hipStream_t st) {
   return decode_head(c, (const float*)cur, nullptr, 0, st);
 }
 
+// the prefill scratch of up to pf_items prompts of Lp positions (one layer slot, the residual stream's three [M, H] slots, the pass's key mask and index rows)
+static size_t prefill_scratch_layout(const opadpo_dims& d, opadpo_saved& pf, int pf_items, int Lp, void* base, Carve* rest = nullptr) {
+  const int M = pf_items * Lp;
+  pf.S = pf_items; pf.L = Lp; pf.T = 1; pf.K = 1; pf.M = M; pf.R = pf_items; pf.train = 0; pf.nb = 1;
+  Carve cv(base);
+  pf.x = cv.take<float>(3 * (size_t)M * d.hidden);
+  pf.lb = carve_layer_bufs(cv, d, 1, M, pf_items, Lp);
+  pf.key_mask = cv.take<uint8_t>((size_t)pf_items * Lp); pf.rows = cv.take<int32_t>(pf_items);
+  pf.labels = cv.take<int32_t>(pf_items);       // reused as feat_row = arange(items of a pass): every prompt carries its own image
+  if (rest) *rest = cv;
+  return cv.off;
+}
+// one prefill pass through the full-sequence kernels: n <= pf.S prompts (ids / text_mask [n, Q], feats [n, P, H]), their K / V into n consecutive
+// sequences of every layer's cache starting at kc0 / vc0 (layers per_layer elements apart, kv_len slots per sequence), their last hidden rows into
+// hs [n, H] (residual adds deferred: h into hs and the down-projection's product into xs).  after_splice() runs once the pass's key mask exists.
+extern "C++" template <class AfterSplice>
+static hipError_t prefill_pass(opadpo_ctx* c, const opadpo_ctx::Adapter& ad, opadpo_saved& pf, const int32_t* ids, const uint8_t* text_mask,
+                               const uint16_t* feats, int n, int Q, bf16_t* kc0, bf16_t* vc0, size_t per_layer, int kv_len, float* hs, float* xs,
+                               AfterSplice&& after_splice, hipStream_t st) {
+  const opadpo_dims& d = c->d;
+  const int side = d.image_size / d.patch, P = side * side, H = d.hidden, Lp = pf.L;
+  const size_t MH = (size_t)pf.M * H;
+  const LayerBufs pb = slot(d, &pf, 0);
+  float* const Yp = pf.x + 2 * MH;
+  const bool fr = !c->resid_deferred;              // residual adds in the projections' epilogues: a layer writes its output into the other x slot
+  hipLaunchKernelGGL(affine_index_kernel, g1(n), dim3(256), 0, st, pf.labels, n, 1, 0);       // feat_row = arange(n)
+  TRY(hipGetLastError());
+  TRY(launch_embed_splice(ids, text_mask, c->embed, feats, pf.labels, nullptr, pf.x, 1, pf.key_mask, n, Q, P, H, OPADPO_IMAGE_TOKEN, st));
+  TRY(after_splice());
+  const float* yin = nullptr;
+  const float* xin = pf.x;
+  for (int i = 0; i < d.n_layers; ++i) {
+    float* const xo = fr ? pf.x + (size_t)((i + 1) & 1) * MH : Yp;
+    TRY(layer_fwd(c, i, ad, fr ? xin : (i == 0 ? pf.x : pb.h), yin, pf.x + (size_t)(i & 1) * MH, xo, pb, n, Lp, pf.key_mask, 0, 0, kc0 + i * per_layer,
+                  vc0 + i * per_layer, kv_len, st));
+    if (fr) xin = xo; else yin = Yp;
+  }
+  hipLaunchKernelGGL(affine_index_kernel, g1(n), dim3(256), 0, st, pf.rows, n, Lp, Lp - 1);
+  TRY(hipGetLastError());
+  if (fr) return launch_gather_rows((const bf16_t*)xin, 2 * H, pf.rows, (bf16_t*)hs, n, 2 * H, st);   // last position of the last layer's output
+  TRY(launch_gather_rows((const bf16_t*)pb.h, 2 * H, pf.rows, (bf16_t*)hs, n, 2 * H, st));            // last position: x = h + y, added by the head's norm
+  return launch_gather_rows((const bf16_t*)Yp, 2 * H, pf.rows, (bf16_t*)xs, n, 2 * H, st);
+}
+
 // beams = 0: sampling rollout of B rows; beams = k: beam search over B items x k rows (the prefill runs on the B items only);
 // nret = n >= 2 (beams = 0): sampling rollout of B items x n rows off one prefill of the items
 static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats, int items,
@@ -1493,7 +1558,7 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
   // the prefill of more than 64 queries runs in passes of 64: its scratch (and the 32-bit offsets of its GEMMs) stay those of a 64-query rollout,
   // and every kernel of it computes a row independently of how many rows share the launch - the results are those of one pass
   const int pf_items = std::min(items, 64);
-  const int Lp = Q + P - 1, max_ctx = Lp + max_new_tokens, M = pf_items * Lp;
+  const int Lp = Q + P - 1, max_ctx = Lp + max_new_tokens;
   const int kv_len = shared ? Lp : max_ctx;               // cache slots per prefill sequence
   CK(ensure_rope(c, max_ctx, st));
   opadpo_ctx::Decode& D = c->dec;
@@ -1533,6 +1598,10 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
     b.t_gu = cv.take<bf16_t>((size_t)B * 2 * r); b.gu = cv.take<bf16_t>((size_t)B * 2 * F); b.act = cv.take<bf16_t>((size_t)B * F); b.t_d = cv.take<bf16_t>((size_t)B * r);
     D.rstd = b.rstd1 = b.rstd2 = cv.take<float>(B); b.lse = nullptr; D.emb = cv.take<bf16_t>((size_t)B * H); D.logits = cv.take<float>((size_t)B * V);
     D.cur_tok = cv.take<int32_t>(B); D.finished = cv.take<uint8_t>(B); D.step_d = cv.take<int32_t>(1); D.pos_d = cv.take<int32_t>(1);
+    if (D.cont) {
+      D.pos_rows = cv.take<int32_t>(B); D.step_rows = cv.take<int32_t>(B); D.cap_rows = cv.take<int32_t>(B); D.seed_rows = cv.take<uint64_t>(B);
+      D.hist_rows = cv.take<int32_t>((size_t)B * max_new_tokens);
+    }
     D.ws = cv.take<uint8_t>(std::max<size_t>(D.ws_bytes, 4));
     D.part_o = cv.take<float>(D.use64 ? (size_t)D.split_o * B * H : 1);
     D.part_d = cv.take<float>(D.use64 ? (size_t)D.split_d * B * H : 1);
@@ -1546,60 +1615,54 @@ static int decode_begin_impl(opadpo_ctx* c, const char* fn, int adapter_id, cons
   layout(D.arena);
   if (beams) { D.bs.cur_tok = D.cur_tok; D.finished = D.bs.done; }       // a beam decode's finished flags are its items' done flags
   D.active = true;
+  if (D.cont) {
+    // continuous rollout: no prompt yet.  Every slot starts idle - finished, position 0 under an all-zero key mask row (a step's attention of such
+    // a slot reads no cache slot and folds no key: its output is 0), step 0 under cap 0, pad as its current token and in its history row
+#define CKC(expr)                                                           \
+  do {                                                                      \
+    hipError_t e_ = (expr);                                                 \
+    if (e_ != hipSuccess) { opadpo_decode_end(c); return cfail(c, e_, fn); } \
+  } while (0)
+    CKC(hipMemsetAsync(D.key_mask, 0, (size_t)B * max_ctx, st));
+    CKC(hipMemsetAsync(D.finished, 1, B, st));
+    CKC(hipMemsetAsync(D.pos_rows, 0, B * sizeof(int32_t), st));
+    CKC(hipMemsetAsync(D.step_rows, 0, B * sizeof(int32_t), st));
+    CKC(hipMemsetAsync(D.cap_rows, 0, B * sizeof(int32_t), st));
+    CKC(hipMemsetAsync(D.seed_rows, 0, B * sizeof(uint64_t), st));
+    CKC(hipMemsetAsync(D.hs, 0, (size_t)B * H * sizeof(float), st));      // the admission head normalises every slot's row: rows never admitted stay finite
+    CKC(hipMemsetAsync(D.x, 0, (size_t)B * H * sizeof(float), st));
+    std::vector<int32_t> pad((size_t)max_new_tokens * B, pad_id);
+    CKC(hipMemcpyAsync(D.cur_tok, pad.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    CKC(hipMemcpyAsync(D.hist_rows, pad.data(), pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    CKC(hipStreamSynchronize(st));
+#undef CKC
+    D.slot_free.assign(B, 1);
+    return 0;
+  }
   // ---- prefill through the full-sequence kernels (scratch arena released afterwards) ----
   opadpo_saved pf;
-  pf.S = pf_items; pf.L = Lp; pf.T = 1; pf.K = 1; pf.M = M; pf.R = pf_items; pf.train = 0; pf.nb = 1;
-  size_t pbytes = 0;
-  auto playout = [&](void* base) {
-    Carve cv(base);
-    pf.x = cv.take<float>(3 * (size_t)M * H);
-    pf.lb = carve_layer_bufs(cv, d, 1, M, pf_items, Lp);
-    pf.key_mask = cv.take<uint8_t>((size_t)pf_items * Lp); pf.rows = cv.take<int32_t>(pf_items);
-    pf.labels = cv.take<int32_t>(pf_items);       // reused as feat_row = arange(items of a pass): every prompt carries its own image
-    return cv.off;
-  };
-  pbytes = playout(nullptr);
+  const size_t pbytes = prefill_scratch_layout(d, pf, pf_items, Lp, nullptr);
   void* parena = ctx_alloc(c, pbytes, st);
   if (!parena) { opadpo_decode_end(c); return cfail(c, hipErrorOutOfMemory, "opadpo_decode_begin (prefill scratch)"); }
-  playout(parena);
+  prefill_scratch_layout(d, pf, pf_items, Lp, parena);
 #define CKD(expr)                                                                                         \
   do {                                                                                                    \
     hipError_t e_ = (expr);                                                                               \
     if (e_ != hipSuccess) { ctx_free(c, parena, pbytes); opadpo_decode_end(c); return cfail(c, e_, fn); } \
   } while (0)
-  const size_t MH = (size_t)M * H, per_layer = (size_t)items * nh * kv_len * hd;
-  const LayerBufs pb = slot(d, &pf, 0);
-  float* const Yp = pf.x + 2 * MH;
-  const bool fr = !c->resid_deferred;              // residual adds in the projections' epilogues: a layer writes its output into the other x slot
+  const size_t per_layer = (size_t)items * nh * kv_len * hd;
+  const bool fr = !c->resid_deferred;              // residual adds in the projections' epilogues: the last hidden row is the last layer's output
   for (int s0 = 0; s0 < items; s0 += pf_items) {   // one pass per pf_items queries (one pass up to 64 queries)
     const int n = std::min(pf_items, items - s0);
     const size_t kv0 = (size_t)s0 * nh * kv_len * hd;      // the pass's first sequence inside a layer's cache
-    hipLaunchKernelGGL(affine_index_kernel, g1(n), dim3(256), 0, st, pf.labels, n, 1, 0);       // feat_row = arange(n)
-    CKD(hipGetLastError());
-    CKD(launch_embed_splice(ids + (size_t)s0 * Q, text_mask + (size_t)s0 * Q, c->embed, feats + (size_t)s0 * P * H, pf.labels, nullptr, pf.x, 1, pf.key_mask, n, Q, P, H,
-                            OPADPO_IMAGE_TOKEN, st));
-    if (beams) CKD(hipMemcpyAsync(D.key_mask, pf.key_mask, (size_t)items * Lp, hipMemcpyDeviceToDevice, st));    // the prefix mask; suffix keys are all visible (B * k <= 64: one pass)
-    else if (nret) CKD(hipMemcpyAsync(D.key_mask + (size_t)s0 * Lp, pf.key_mask, (size_t)n * Lp, hipMemcpyDeviceToDevice, st));      // the pass's rows of the prefix mask
-    else {
+    auto mask = [&]() -> hipError_t {
+      if (beams) return hipMemcpyAsync(D.key_mask, pf.key_mask, (size_t)items * Lp, hipMemcpyDeviceToDevice, st);    // the prefix mask; suffix keys are all visible (B * k <= 64: one pass)
+      if (nret) return hipMemcpyAsync(D.key_mask + (size_t)s0 * Lp, pf.key_mask, (size_t)n * Lp, hipMemcpyDeviceToDevice, st);      // the pass's rows of the prefix mask
       hipLaunchKernelGGL(decode_mask_kernel, g1((size_t)n * max_ctx), dim3(256), 0, st, pf.key_mask, D.key_mask + (size_t)s0 * max_ctx, n, Lp, max_ctx);
-      CKD(hipGetLastError());
-    }
-    const float* yin = nullptr;
-    const float* xin = pf.x;
-    for (int i = 0; i < d.n_layers; ++i) {
-      float* const xo = fr ? pf.x + (size_t)((i + 1) & 1) * MH : Yp;
-      CKD(layer_fwd(c, i, ad, fr ? xin : (i == 0 ? pf.x : pb.h), yin, pf.x + (size_t)(i & 1) * MH, xo, pb, n, Lp, pf.key_mask, 0, 0, D.kc + i * per_layer + kv0,
-                    D.vc + i * per_layer + kv0, kv_len, st));
-      if (fr) xin = xo; else yin = Yp;
-    }
-    hipLaunchKernelGGL(affine_index_kernel, g1(n), dim3(256), 0, st, pf.rows, n, Lp, Lp - 1);
-    CKD(hipGetLastError());
-    float* const hs = D.hs + (size_t)s0 * H;
-    if (fr) CKD(launch_gather_rows((const bf16_t*)xin, 2 * H, pf.rows, (bf16_t*)hs, n, 2 * H, st));   // last position of the last layer's output
-    else {
-      CKD(launch_gather_rows((const bf16_t*)pb.h, 2 * H, pf.rows, (bf16_t*)hs, n, 2 * H, st));        // last position: x = h + y, added by the head's norm
-      CKD(launch_gather_rows((const bf16_t*)Yp, 2 * H, pf.rows, (bf16_t*)(D.x + (size_t)s0 * H), n, 2 * H, st));
-    }
+      return hipGetLastError();
+    };
+    CKD(prefill_pass(c, ad, pf, ids + (size_t)s0 * Q, text_mask + (size_t)s0 * Q, feats + (size_t)s0 * P * H, n, Q, D.kc + kv0, D.vc + kv0, per_layer, kv_len,
+                     D.hs + (size_t)s0 * H, D.x + (size_t)s0 * H, mask, st));
   }
   CKD(hipMemsetAsync(D.finished, 0, beams ? items : B, st));
   CKD(hipMemsetAsync(D.step_d, 0, sizeof(int32_t), st));
@@ -1836,6 +1899,132 @@ int opadpo_decode_all_finished(opadpo_ctx* c, int* all_finished, void* stream) {
   return 0;
 }
 
+// ---- continuous rollout: a session of `slots` decode rows that are refilled as they finish (header: the contract of the four entry points) ----
+int opadpo_decode_cont_begin(opadpo_ctx* c, int adapter_id, int slots, int Q, int max_new_tokens, float temperature, int top_k, float top_p, int eos_id,
+                             int pad_id, int suppress_eos, void* stream) {
+  if (!c) return (int)hipErrorInvalidValue;
+  // both settings are for THIS call, accepted or refused (as in opadpo_decode_begin)
+  const bool logit_armed = !c->next_logit.bias_ids.empty() || !c->next_logit.score_ids.empty();
+  c->next_logit = {};
+  const opadpo_ctx::LogprobArm lp = c->next_lp;
+  c->next_lp = {};
+  if (slots < 1 || slots > 256) return cbad(c, __func__, "slots must be in 1..256 (the decode GEMMs take at most 256 rows per device)");
+  if (logit_armed)
+    return cbad(c, __func__, "logit bias / first-token scores (opadpo_ctx_set_logit_processors) are not supported by a continuous session: they keep the static rollout (opadpo_decode_begin)");
+  if (!weights_ready(c)) return cbad(c, __func__, "LLM weights not set");
+  if (adapter_id < 0 || adapter_id >= OPADPO_MAX_ADAPTERS) return cbad(c, __func__, "adapter id out of range");
+  if (Q <= 0 || max_new_tokens <= 0 || temperature <= 0.f) return cbad(c, __func__, "bad shape: need Q >= 1, max_new_tokens >= 1, temperature > 0");
+  if (lp.logp && c->d.vocab % 4) return cbad(c, __func__, "per-token log-probs (opadpo_ctx_set_output_logprobs) need vocab % 4 == 0 (opadpo_token_logprobs reads 16 bytes at a time)");
+  opadpo_decode_end(c);
+  c->dec.lp = lp;
+  c->dec.cont = true; c->dec.Q = Q;
+  return decode_begin_impl(c, __func__, adapter_id, nullptr, nullptr, nullptr, slots, Q, 0, 0, max_new_tokens, temperature, top_k, top_p, 0, eos_id, pad_id,
+                           suppress_eos, nullptr, (hipStream_t)stream);
+}
+
+int opadpo_decode_cont_admit(opadpo_ctx* c, int n, const int32_t* slot_ids, const int32_t* ids, const uint8_t* text_mask, const uint16_t* feats,
+                             const uint64_t* seeds, const int32_t* caps, void* stream) {
+  if (!c) return (int)hipErrorInvalidValue;
+  opadpo_ctx::Decode& D = c->dec;
+  if (!D.active || !D.cont) return cbad(c, __func__, "no active continuous session (call opadpo_decode_cont_begin)");
+  if (n == 0) return 0;
+  if (n < 0 || n > D.B) return cbad(c, __func__, "n must be in 0..slots");
+  if (!slot_ids || !ids || !text_mask || !feats || !seeds || !caps) return cbad(c, __func__, "null operand");
+  std::vector<uint8_t> seen(D.B, 0);
+  for (int j = 0; j < n; ++j) {
+    const int s = slot_ids[j];
+    if (s < 0 || s >= D.B) return cbad(c, __func__, "slot id outside 0..slots-1");
+    if (seen[s]) return cbad(c, __func__, "slot id repeated in one admission");
+    seen[s] = 1;
+    if (!D.slot_free[s]) return cbad(c, __func__, "admission into a slot that is not finished (as of the last opadpo_decode_cont_poll)");
+    if (caps[j] < 1 || caps[j] > D.max_new) return cbad(c, __func__, "cap must be in 1..max_new_tokens of the session");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const opadpo_dims& d = c->d;
+  const opadpo_ctx::Adapter& ad = c->adapters[D.adapter];
+  const int side = d.image_size / d.patch, P = side * side, H = d.hidden, nh = d.n_heads, hd = d.head_dim, Q = D.Q, Lp = D.Lp, max_ctx = D.max_ctx;
+  // prompts whose slots are consecutive share a prefill pass (at most 64 per pass, as in opadpo_decode_begin): run j0 .. j1-1
+  std::vector<int> run_end(n);
+  int longest = 1;
+  for (int j0 = 0; j0 < n;) {
+    int j1 = j0 + 1;
+    while (j1 < n && j1 - j0 < 64 && slot_ids[j1] == slot_ids[j1 - 1] + 1) ++j1;
+    run_end[j0] = j1;
+    longest = std::max(longest, j1 - j0);
+    j0 = j1;
+  }
+  // the prefill scratch, allocated and released per admission, with the device copies of the three host arrays behind it
+  opadpo_saved pf;
+  int32_t *slot_d = nullptr, *cap_d = nullptr; uint64_t* seed_d = nullptr;
+  auto layout = [&](void* base) {
+    Carve cv(nullptr);
+    prefill_scratch_layout(d, pf, longest, Lp, base, &cv);
+    seed_d = cv.take<uint64_t>(n); slot_d = cv.take<int32_t>(n); cap_d = cv.take<int32_t>(n);
+    return cv.off;
+  };
+  const size_t pbytes = layout(nullptr);
+  void* parena = ctx_alloc(c, pbytes, st);
+  if (!parena) { opadpo_decode_end(c); return cfail(c, hipErrorOutOfMemory, "opadpo_decode_cont_admit (prefill scratch)"); }
+  layout(parena);
+#define CKA(expr)                                                                                               \
+  do {                                                                                                          \
+    hipError_t e_ = (expr);                                                                                     \
+    if (e_ != hipSuccess) { ctx_free(c, parena, pbytes); opadpo_decode_end(c); return cfail(c, e_, __func__); } \
+  } while (0)
+  CKA(hipMemcpyAsync(slot_d, slot_ids, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  CKA(hipMemcpyAsync(seed_d, seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  CKA(hipMemcpyAsync(cap_d, caps, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  CKA(launch_decode_rows_admit(slot_d, seed_d, cap_d, n, Lp, D.max_new, D.pad_id, D.pos_rows, D.step_rows, D.cap_rows, D.seed_rows, D.finished, D.hist_rows,
+                               D.lp.logp, D.lp.ent, st));
+  const size_t per_layer = (size_t)D.B * nh * max_ctx * hd;
+  for (int j0 = 0; j0 < n; j0 = run_end[j0]) {
+    const int m = run_end[j0] - j0, s0 = slot_ids[j0];
+    const size_t kv0 = (size_t)s0 * nh * max_ctx * hd;     // the run's first slot inside a layer's cache
+    auto mask = [&]() -> hipError_t {                      // the slots' key-mask rows: the prompt's mask, then ones
+      hipLaunchKernelGGL(decode_mask_kernel, g1((size_t)m * max_ctx), dim3(256), 0, st, pf.key_mask, D.key_mask + (size_t)s0 * max_ctx, m, Lp, max_ctx);
+      return hipGetLastError();
+    };
+    CKA(prefill_pass(c, ad, pf, ids + (size_t)j0 * Q, text_mask + (size_t)j0 * Q, feats + (size_t)j0 * P * H, m, Q, D.kc + kv0, D.vc + kv0, per_layer, max_ctx,
+                     D.hs + (size_t)s0 * H, D.x + (size_t)s0 * H, mask, st));
+  }
+  // token 0 of the admitted slots: the head on every slot's row, as opadpo_decode_begin runs it on a batch of this many rows (the rows of the other
+  // slots are stale and unread), the sampler and the log-prob kernel on the admitted slots only, each under its slot's row id
+  const bool fr = !c->resid_deferred;
+  CKA(fr ? decode_head(c, D.hs, nullptr, 0, st, D.B, slot_d, n) : decode_head(c, D.hs, D.x, 1, st, D.B, slot_d, n));
+  CKA(hipStreamSynchronize(st));
+#undef CKA
+  ctx_free(c, parena, pbytes);
+  for (int j = 0; j < n; ++j) D.slot_free[slot_ids[j]] = 0;
+  return 0;
+}
+
+int opadpo_decode_cont_poll(opadpo_ctx* c, uint8_t* finished_host, void* stream) {
+  if (!c) return (int)hipErrorInvalidValue;
+  opadpo_ctx::Decode& D = c->dec;
+  if (!D.active || !D.cont) return cbad(c, __func__, "no active continuous session (call opadpo_decode_cont_begin)");
+  if (!finished_host) return cbad(c, __func__, "null operand");
+  CK(hipMemcpyAsync(D.slot_free.data(), D.finished, D.B, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  CK(hipStreamSynchronize((hipStream_t)stream));
+  for (int s = 0; s < D.B; ++s) finished_host[s] = D.slot_free[s];
+  return 0;
+}
+
+int opadpo_decode_cont_retire(opadpo_ctx* c, int slot, int32_t* tokens, float* logp, float* ent, void* stream) {
+  if (!c) return (int)hipErrorInvalidValue;
+  opadpo_ctx::Decode& D = c->dec;
+  if (!D.active || !D.cont) return cbad(c, __func__, "no active continuous session (call opadpo_decode_cont_begin)");
+  if (slot < 0 || slot >= D.B) return cbad(c, __func__, "slot id outside 0..slots-1");
+  if (!tokens) return cbad(c, __func__, "null operand");
+  if (!D.slot_free[slot]) return cbad(c, __func__, "the slot is not finished (as of the last opadpo_decode_cont_poll)");
+  if ((logp && !D.lp.logp) || (ent && !D.lp.ent)) return cbad(c, __func__, "log-probs / entropies were not armed for this session (opadpo_ctx_set_output_logprobs)");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t T = (size_t)D.max_new, o = (size_t)slot * T;
+  CK(hipMemcpyAsync(tokens, D.hist_rows + o, T * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  if (logp) CK(hipMemcpyAsync(logp, D.lp.logp + o, T * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (ent) CK(hipMemcpyAsync(ent, D.lp.ent + o, T * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
 int opadpo_decode_end(opadpo_ctx* c) {
   if (!c) return (int)hipErrorInvalidValue;
   opadpo_ctx::Decode& D = c->dec;
@@ -1844,6 +2033,7 @@ int opadpo_decode_end(opadpo_ctx* c) {
   if (D.cap_stream) { (void)hipStreamSynchronize(D.cap_stream); }
   if (D.active) { ctx_free(c, D.arena, D.bytes); D.arena = nullptr; D.active = false; }
   D.beams = 0; D.items = 0; D.nret = 0;
+  D.cont = false; D.slot_free.clear();
   D.logit = {}; D.bias_ids = nullptr; D.score_ids = nullptr; D.bias = nullptr;
   c->next_logit = {};
   D.lp = {}; c->next_lp = {};

@@ -35,22 +35,29 @@ namespace {
 // writes its (max, sum, out) partial into slot slot0 + split of the row's `slots` slots, whatever gridDim.z is.
 struct BeamDec { const int32_t* table; long long tstride; int Lp, max_new, k; };
 struct SharedDec : BeamDec { int key0, slots, slot0; };
+// ROWS (one RowsDec after the last argument; continuous rollout, FUSE only, opadpo_attn_decode_fused_rows): ctx_ptr is an array [B] and row b sits at its
+// OWN position ctx_ptr[b] - the rows of one launch have different context lengths.  Everything below depends on the row's ctx alone (the key ranges,
+// `per`, the block that appends), so row b computes what the fused kernel computes for it when every row sits at ctx_ptr[b].  The position is clamped
+// into [0, max_ctx - 1]: an idle slot never indexes the RoPE tables, the caches or the key mask outside its own extent.
+struct RowsDec {};
 template <int HD, int NW, bool FUSE = false, typename... BA>
 __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const bf16_t* q, int ldq, const bf16_t* kc, const bf16_t* vc,
                                                                bf16_t* o, const uint8_t* key_mask, int nh, int ctx_arg,
                                                                const int32_t* ctx_ptr, int max_ctx, float scale_log2e, float* ws_part,
                                                                const float* cosb = nullptr, const float* sinb = nullptr,
                                                                bf16_t* kc_w = nullptr, bf16_t* vc_w = nullptr, BA... beam) {
-  constexpr bool BEAM = sizeof...(BA) > 0;
+  constexpr bool ROWS = (std::is_same_v<BA, RowsDec> || ...);
+  constexpr bool BEAM = sizeof...(BA) > 0 && !ROWS;
   constexpr bool SHARED = (std::is_same_v<BA, SharedDec> || ...);
-  static_assert(!BEAM || FUSE, "the beam form appends the new token: FUSE only");
+  static_assert((!BEAM && !ROWS) || FUSE, "the beam and per-row-position forms append the new token: FUSE only");
   constexpr int LPK = HD / 8;            // lanes per key
   constexpr int KPW = 64 / LPK;          // keys per wave step
   constexpr int NG = NW * KPW;           // lane groups (= keys per block step)
   constexpr int U = 4;
   __shared__ float sm_m[NG], sm_l[NG];
   __shared__ __attribute__((aligned(16))) float sm_acc[NG][HD];
-  const int ctx = ctx_ptr ? min(ctx_ptr[0] + 1, max_ctx) : ctx_arg;   // device-resident: keys 0..pos (graph replay)
+  const int ctx = ROWS ? min(max(ctx_ptr[blockIdx.y], 0) + 1, max_ctx)      // the row's own position, held inside its cache
+                       : ctx_ptr ? min(ctx_ptr[0] + 1, max_ctx) : ctx_arg;   // device-resident: keys 0..pos (graph replay)
   const int h = blockIdx.x, b = blockIdx.y, split = blockIdx.z, splits = gridDim.z;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane / LPK, d = lane % LPK;
@@ -481,17 +488,60 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
   return x ^ (x >> 31);
 }
 
+// Per-row form of both samplers (one SampRows after the last argument; continuous rollout, opadpo_sample_rows): row = slot.  The draw stays
+// f(seed, step, row) with seed = seed[row] and step = step[row]; the token goes to the slot's OWN history row, history [rows, max_steps] at
+// [row, step]; the writer then advances step[row] and marks the row finished when it drew EOS or wrote its cap[row]-th token.  A finished row - or
+// one whose step is not inside [0, min(cap, max_steps)), which only a caller's mistake produces - emits pad into `out` and touches nothing else:
+// no history slot, no step.  ids (nullable): workgroup i samples row ids[i] (the admitted slots of a running session; logits row = the slot's).
+struct SampRows { const uint64_t* seed; int32_t* step; const int32_t* cap; const int32_t* ids; int max_steps; };
+// the one place a sampled token (or the pad of an empty kept set: eos = false) leaves the kernel
+template <bool ROWS>
+__device__ __forceinline__ void sample_emit(int row, int rows, int tok, uint64_t step, bool eos, uint8_t* finished, int eos_id, int32_t* out,
+                                            int32_t* history, const SampRows& sr) {
+  out[row] = tok;
+  if constexpr (ROWS) {
+    if (history) history[(size_t)row * sr.max_steps + step] = tok;
+    sr.step[row] = (int32_t)step + 1;
+    if ((eos && eos_id >= 0 && tok == eos_id) || (int)step + 1 >= sr.cap[row]) finished[row] = 1;
+  } else {
+    if (history) history[step * rows + row] = tok;
+    if (eos && finished && eos_id >= 0 && tok == eos_id) finished[row] = 1;
+  }
+}
+// the per-row form's row, seed and step; true: the row is idle (finished, or its step outside its extent) and has emitted pad
+template <bool ROWS>
+__device__ __forceinline__ bool sample_row_state(const SampRows& sr, const uint8_t* finished, int pad_id, int32_t* out, int tid, int& row, uint64_t& seed,
+                                                 uint64_t& step) {
+  if constexpr (ROWS) {
+    if (sr.ids) row = sr.ids[row];
+    const int s = sr.step[row];
+    if (finished[row] || s < 0 || s >= sr.cap[row] || s >= sr.max_steps) {
+      if (tid == 0) out[row] = pad_id;
+      return true;
+    }
+    seed = sr.seed[row];
+    step = (uint64_t)s;
+  }
+  return false;
+}
+
 // step_ptr (nullable): device-resident step counter (graph replay) used for the RNG stream and, with `history`
 // ([max_steps, rows]), for the slot the token is appended to.  eos_id >= 0: a row that samples EOS is marked finished.
+template <typename... RA>
 __global__ __launch_bounds__(256) void sample_kernel_generic(const float* logits, int ldl, int V, float inv_temp, int top_k, float top_p,
                                                       uint64_t seed, uint64_t step_arg, const int32_t* step_ptr, uint8_t* finished,
-                                                      int pad_id, int eos_id, int32_t* out, int32_t* history) {
-  const uint64_t step = step_ptr ? (uint64_t)step_ptr[0] : step_arg;
+                                                      int pad_id, int eos_id, int32_t* out, int32_t* history, RA... ra) {
+  constexpr bool ROWS = sizeof...(RA) > 0;
+  uint64_t step = step_ptr ? (uint64_t)step_ptr[0] : step_arg;
   __shared__ float red[4];
   __shared__ float scan[256];
   __shared__ uint32_t s_thr;
-  const int row = blockIdx.x, tid = threadIdx.x;
-  if (finished && finished[row]) {
+  int row = blockIdx.x;
+  const int tid = threadIdx.x;
+  SampRows sr{};
+  if constexpr (ROWS) sr = (ra, ...);
+  if (sample_row_state<ROWS>(sr, finished, pad_id, out, tid, row, seed, step)) return;
+  if (!ROWS && finished && finished[row]) {
     if (tid == 0) {
       out[row] = pad_id;
       if (history) history[step * gridDim.x + row] = pad_id;
@@ -575,9 +625,7 @@ __global__ __launch_bounds__(256) void sample_kernel_generic(const float* logits
         if (run > target) break;
       }
     }
-    out[row] = pick;
-    if (history) history[step * gridDim.x + row] = pick;
-    if (finished && eos_id >= 0 && pick == eos_id) finished[row] = 1;
+    sample_emit<ROWS>(row, gridDim.x, pick, step, true, finished, eos_id, out, history, sr);
   }
 }
 
@@ -638,18 +686,24 @@ __device__ __forceinline__ void pick_digit(const uint64_t* hist, uint64_t base, 
   }
 }
 
+template <typename... RA>
 __global__ __launch_bounds__(SAMP_T) void sample_kernel_fast(const float* logits, int ldl, int V, float inv_temp, int top_k, float top_p,
                                                              uint64_t seed, uint64_t step_arg, const int32_t* step_ptr, uint8_t* finished,
-                                                             int pad_id, int eos_id, int32_t* out, int32_t* history, int compact) {
+                                                             int pad_id, int eos_id, int32_t* out, int32_t* history, int compact, RA... ra) {
+  constexpr bool ROWS = sizeof...(RA) > 0;
   extern __shared__ __attribute__((aligned(16))) float zs[];     // [V] scaled logits
-  const uint64_t step = step_ptr ? (uint64_t)step_ptr[0] : step_arg;
+  uint64_t step = step_ptr ? (uint64_t)step_ptr[0] : step_arg;
   __shared__ uint64_t hist[256];
   __shared__ uint64_t wsum[SAMP_W];
   __shared__ float wmax[SAMP_W];
   __shared__ uint32_t s_digit;
   __shared__ uint64_t s_carry;
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (finished && finished[row]) {
+  int row = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  SampRows sr{};
+  if constexpr (ROWS) sr = (ra, ...);
+  if (sample_row_state<ROWS>(sr, finished, pad_id, out, tid, row, seed, step)) return;
+  if (!ROWS && finished && finished[row]) {
     if (tid == 0) {
       out[row] = pad_id;
       if (history) history[step * gridDim.x + row] = pad_id;
@@ -771,17 +825,10 @@ __global__ __launch_bounds__(SAMP_T) void sample_kernel_fast(const float* logits
         const uint64_t r24 = r >> 40;
         const uint64_t target = (total >> 24) * r24 + (((total & 0xffffffull) * r24) >> 24);
         if (total == 0) {
-          if (lane == 0) {
-            out[row] = pad_id;
-            if (history) history[step * gridDim.x + row] = pad_id;
-          }
+          if (lane == 0) sample_emit<ROWS>(row, gridDim.x, pad_id, step, false, finished, eos_id, out, history, sr);
           return;
         }
-        if (qk > 0 && before <= target && target < before + qk) {
-          out[row] = idx;
-          if (history) history[step * gridDim.x + row] = idx;
-          if (finished && eos_id >= 0 && idx == eos_id) finished[row] = 1;
-        }
+        if (qk > 0 && before <= target && target < before + qk) sample_emit<ROWS>(row, gridDim.x, idx, step, true, finished, eos_id, out, history, sr);
         return;
       }
     }
@@ -843,10 +890,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_kernel_fast(const float* logits
   const uint64_t target = (total >> 24) * r24 + (((total & 0xffffffull) * r24) >> 24);   // floor(u * total) < total
   const uint64_t start = wave_base + incl - local;
   if (total == 0) {
-    if (tid == 0) {
-      out[row] = pad_id;
-      if (history) history[step * gridDim.x + row] = pad_id;
-    }
+    if (tid == 0) sample_emit<ROWS>(row, gridDim.x, pad_id, step, false, finished, eos_id, out, history, sr);
     return;
   }
   if (local > 0 && start <= target && target < start + local) {
@@ -860,9 +904,7 @@ __global__ __launch_bounds__(SAMP_T) void sample_kernel_fast(const float* logits
         run += qm;
       }
     }
-    out[row] = pick;
-    if (history) history[step * gridDim.x + row] = pick;
-    if (finished && eos_id >= 0 && pick == eos_id) finished[row] = 1;
+    sample_emit<ROWS>(row, gridDim.x, pick, step, true, finished, eos_id, out, history, sr);
   }
 }
 
@@ -962,17 +1004,31 @@ __global__ __launch_bounds__(256) void gather_scores_kernel(const float* logits,
 // by every thread (deterministic).  tok == pad_id: logp = -0.0, ent = 0 without reading the row (head_fwd_kernel's pad rule, by value).
 // step_ptr (nullable): the device step counter of the rollout; the outputs are [max_steps, rows] like `history`, slot step * rows + row;
 // a step at or past max_steps writes nothing.  A token outside [0, V) that is not pad reads NaN.
+// Per-row form (one TlpRows after the last argument; continuous rollout): row = slot (workgroup i reads row ids[i] when ids is given), the outputs are
+// [rows, max_steps] like the per-row sampler's history and the slot is [row, step[row] - 1]: the per-row sampler has advanced the row's step past the
+// token it wrote.  A pad token writes NOTHING here - the row's outputs were set to the pad values when the slot was admitted, and a finished row's
+// step no longer names a slot of its own to write them to.
 constexpr int TLP_T = 1024, TLP_W = TLP_T / 64, TLP_R = 8;
+struct TlpRows { const int32_t* step; const int32_t* ids; };
 
+template <typename... RA>
 __global__ __launch_bounds__(TLP_T) void token_logprob_kernel(const float* logits, int ldl, int V, const int32_t* tokens, float inv_temp, int pad_id,
-                                                              const int32_t* step_ptr, int max_steps, float* logp, float* ent) {
+                                                              const int32_t* step_ptr, int max_steps, float* logp, float* ent, RA... ra) {
+  constexpr bool ROWS = sizeof...(RA) > 0;
   __shared__ float wmax[TLP_W], wse[TLP_W], wsz[TLP_W];
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int step = step_ptr ? step_ptr[0] : 0;
+  int row = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int step = step_ptr ? step_ptr[0] : 0;
+  if constexpr (ROWS) {
+    const TlpRows tr = (ra, ...);
+    if (tr.ids) row = tr.ids[row];
+    step = tr.step[row] - 1;
+  }
   if (step < 0 || step >= max_steps) return;
-  const size_t o = (size_t)step * gridDim.x + row;
+  const size_t o = ROWS ? (size_t)row * max_steps + step : (size_t)step * gridDim.x + row;
   const int tok = tokens[row];
   if (tok == pad_id) {
+    if (ROWS) return;
     if (tid == 0) {
       logp[o] = -0.0f;
       if (ent) ent[o] = 0.0f;
@@ -1249,7 +1305,43 @@ __global__ __launch_bounds__(64) void beam_update_kernel(const float* cand_val, 
   }
 }
 
+// ---- continuous rollout: the per-slot state between two steps (opadpo_decode_cont_begin / _admit) -----------------------------------------------
+// start of a step: a live slot moves to the position of the token it is about to append; a finished (or never used) slot stays where it is, so
+// it re-appends the same key at the same slot of its own cache for as long as it idles.  The clamp is never reached by a live slot (its step is
+// below its cap <= max_new, so its position is below Lp + max_new - 1); it is the bound an idle slot is held to whatever its state.
+__global__ void decode_rows_advance_kernel(int32_t* pos, const uint8_t* finished, int slots, int max_ctx) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < slots && !finished[i]) pos[i] = min(pos[i] + 1, max_ctx - 1);
+}
+// admission: one workgroup per admitted slot.  Position Lp - 1 (the last prefill key), step 0, the prompt's cap and seed, not finished; the slot's
+// history row becomes pad and its log-prob / entropy rows (nullable) the pad values -0.0 / 0.
+__global__ __launch_bounds__(256) void decode_rows_admit_kernel(const int32_t* slot_ids, const uint64_t* seeds, const int32_t* caps, int Lp, int max_new,
+                                                                int pad_id, int32_t* pos, int32_t* step, int32_t* cap, uint64_t* seed,
+                                                                uint8_t* finished, int32_t* history, float* logp, float* ent) {
+  const int j = blockIdx.x, s = slot_ids[j], tid = threadIdx.x;
+  if (tid == 0) { pos[s] = Lp - 1; step[s] = 0; cap[s] = caps[j]; seed[s] = seeds[j]; finished[s] = 0; }
+  for (int t = tid; t < max_new; t += 256) {
+    history[(size_t)s * max_new + t] = pad_id;
+    if (logp) logp[(size_t)s * max_new + t] = -0.0f;
+    if (ent) ent[(size_t)s * max_new + t] = 0.0f;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_decode_rows_advance(int32_t* pos, const uint8_t* finished, int slots, int max_ctx, hipStream_t st) {
+  if (slots <= 0) return hipSuccess;
+  hipLaunchKernelGGL(decode_rows_advance_kernel, dim3((slots + 255) / 256), dim3(256), 0, st, pos, finished, slots, max_ctx);
+  return hipGetLastError();
+}
+// slot_ids / seeds / caps: device arrays [n]; the caller has checked every slot id against the session's slot count and every cap against max_new
+hipError_t launch_decode_rows_admit(const int32_t* slot_ids, const uint64_t* seeds, const int32_t* caps, int n, int Lp, int max_new, int pad_id, int32_t* pos,
+                                    int32_t* step, int32_t* cap, uint64_t* seed, uint8_t* finished, int32_t* history, float* logp, float* ent, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(decode_rows_admit_kernel, dim3(n), dim3(256), 0, st, slot_ids, seeds, caps, Lp, max_new, pad_id, pos, step, cap, seed, finished, history,
+                     logp, ent);
+  return hipGetLastError();
+}
 
 static int attn_decode_splits(int B, int nh, int max_ctx) {
   // 257..767 (sequence, head) pairs (9..23 sequences at 32 heads): two key ranges per pair, run as 4-wave workgroups (>= 512 of them) - measured
@@ -1290,6 +1382,27 @@ hipError_t launch_attn_decode_fused(const bf16_t* qkv, int ld, const float* cosb
   if (hd == 128) { if (fat) ADF(128, 16); else ADF(128, 4); }
   else           { if (fat) ADF(64, 16); else ADF(64, 4); }
 #undef ADF
+  if (splits > 1) hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(B * nh), dim3(hd), 0, st, part, o, splits, hd);
+  return hipGetLastError();
+}
+
+// the fused launch with a position per row (continuous rollout): the split rule, the workgroup shape and the merge of launch_attn_decode_fused
+hipError_t launch_attn_decode_fused_rows(const bf16_t* qkv, int ld, const float* cosb, const float* sinb, bf16_t* kc, bf16_t* vc, bf16_t* o,
+                                         const uint8_t* key_mask, int B, int nh, int hd, const int32_t* pos_rows, int max_ctx, float scale,
+                                         void* workspace, size_t workspace_bytes, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  if ((hd != 64 && hd != 128) || !pos_rows || ld % 8 || max_ctx < 1) return hipErrorInvalidValue;
+  int splits = attn_decode_splits(B, nh, max_ctx);
+  if (splits > 1 && (!workspace || workspace_bytes < attn_decode_workspace_bytes(B, nh, hd, max_ctx))) splits = 1;
+  float* part = (float*)workspace;
+  const float sl2 = scale * 1.4426950408889634f;
+  const bool fat = attn_decode_fat(B, nh, splits);
+  const dim3 gr(nh, B, splits);
+#define ADR(HD_, NW_) hipLaunchKernelGGL((attn_decode_kernel<HD_, NW_, true, RowsDec>), gr, dim3(NW_ * 64), 0, st, qkv, ld, kc, vc, o, key_mask, nh, 0, pos_rows, \
+                                         max_ctx, sl2, part, cosb, sinb, kc, vc, RowsDec{})
+  if (hd == 128) { if (fat) ADR(128, 16); else ADR(128, 4); }
+  else           { if (fat) ADR(64, 16); else ADR(64, 4); }
+#undef ADR
   if (splits > 1) hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(B * nh), dim3(hd), 0, st, part, o, splits, hd);
   return hipGetLastError();
 }
@@ -1433,18 +1546,45 @@ hipError_t launch_sample(const float* logits, int ldl, int rows, int V, float te
   const bool fast = V % 4 == 0 && ldl % 4 == 0 && V <= SAMP_MAXV && ((uintptr_t)logits & 15) == 0;
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)sample_kernel_fast, hipFuncAttributeMaxDynamicSharedMemorySize, SAMP_MAXV * 4);
+    (void)hipFuncSetAttribute((const void*)sample_kernel_fast<>, hipFuncAttributeMaxDynamicSharedMemorySize, SAMP_MAXV * 4);
     attr_set = true;
   }
   // compact (default): one-wave tail on the kept tokens after the top-k threshold; process flag bit 9: the full vocabulary sweeps (identical
   // draws; the exactness test's yardstick).  A process flag: the same for eager and captured launches
   const int compact = process_flags().sample_compact ? 1 : 0;
   if (fast)
-    hipLaunchKernelGGL(sample_kernel_fast, dim3(rows), dim3(SAMP_T), (size_t)V * 4, st, logits, ldl, V, 1.0f / temperature, top_k, top_p, seed,
+    hipLaunchKernelGGL(sample_kernel_fast<>, dim3(rows), dim3(SAMP_T), (size_t)V * 4, st, logits, ldl, V, 1.0f / temperature, top_k, top_p, seed,
                        step, step_ptr, finished, pad_id, eos_id, out, history, compact);
   else
-    hipLaunchKernelGGL(sample_kernel_generic, dim3(rows), dim3(256), 0, st, logits, ldl, V, 1.0f / temperature, top_k, top_p, seed,
+    hipLaunchKernelGGL(sample_kernel_generic<>, dim3(rows), dim3(256), 0, st, logits, ldl, V, 1.0f / temperature, top_k, top_p, seed,
                        step, step_ptr, finished, pad_id, eos_id, out, history);
+  return hipGetLastError();
+}
+
+// the per-row form (SampRows): the same choice between the two kernels, the same compact flag.  n_ids > 0: only the rows ids[0 .. n_ids) (device
+// array, every entry in [0, rows): the caller's check) are sampled.  hipErrorInvalidValue, nothing launched: a null seed / step / cap / finished /
+// out array, max_steps < 1, temperature <= 0.
+hipError_t launch_sample_rows(const float* logits, int ldl, int rows, int V, float temperature, int top_k, float top_p, const uint64_t* seed_rows,
+                              int32_t* step_rows, const int32_t* cap_rows, int max_steps, const int32_t* ids, int n_ids, uint8_t* finished, int pad_id,
+                              int eos_id, int32_t* out, int32_t* history, hipStream_t st) {
+  if (rows <= 0) return hipSuccess;
+  if (!logits || !seed_rows || !step_rows || !cap_rows || !finished || !out || max_steps < 1 || !(temperature > 0.f) || n_ids < 0 || n_ids > rows)
+    return hipErrorInvalidValue;
+  const bool fast = V % 4 == 0 && ldl % 4 == 0 && V <= SAMP_MAXV && ((uintptr_t)logits & 15) == 0;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)sample_kernel_fast<SampRows>, hipFuncAttributeMaxDynamicSharedMemorySize, SAMP_MAXV * 4);
+    attr_set = true;
+  }
+  const int compact = process_flags().sample_compact ? 1 : 0;
+  const SampRows sr{seed_rows, step_rows, cap_rows, n_ids > 0 ? ids : nullptr, max_steps};
+  const int blocks = n_ids > 0 ? n_ids : rows;
+  if (fast)
+    hipLaunchKernelGGL(sample_kernel_fast<SampRows>, dim3(blocks), dim3(SAMP_T), (size_t)V * 4, st, logits, ldl, V, 1.0f / temperature, top_k, top_p,
+                       (uint64_t)0, (uint64_t)0, nullptr, finished, pad_id, eos_id, out, history, compact, sr);
+  else
+    hipLaunchKernelGGL(sample_kernel_generic<SampRows>, dim3(blocks), dim3(256), 0, st, logits, ldl, V, 1.0f / temperature, top_k, top_p, (uint64_t)0,
+                       (uint64_t)0, nullptr, finished, pad_id, eos_id, out, history, sr);
   return hipGetLastError();
 }
 
@@ -1477,7 +1617,19 @@ hipError_t launch_token_logprobs(const float* logits, int ldl, int rows, int V, 
   if (rows < 1 || V <= 0 || V % 4 || ldl % 4 || ldl < V || !(temperature >= 0.f) || max_steps < 1) return hipErrorInvalidValue;
   if (!logits || !tokens || !logp || ((uintptr_t)logits & 15)) return hipErrorInvalidValue;
   const float inv_temp = temperature == 0.f ? 1.0f : 1.0f / temperature;
-  hipLaunchKernelGGL(token_logprob_kernel, dim3(rows), dim3(TLP_T), 0, st, logits, ldl, V, tokens, inv_temp, pad_id, step_ptr, max_steps, logp, ent);
+  hipLaunchKernelGGL(token_logprob_kernel<>, dim3(rows), dim3(TLP_T), 0, st, logits, ldl, V, tokens, inv_temp, pad_id, step_ptr, max_steps, logp, ent);
+  return hipGetLastError();
+}
+
+// the per-row form (TlpRows), launched right after launch_sample_rows with the same ids: logp / ent [rows, max_steps]; same refusals
+hipError_t launch_token_logprobs_rows(const float* logits, int ldl, int rows, int V, const int32_t* tokens, float temperature, int pad_id,
+                                      const int32_t* step_rows, int max_steps, const int32_t* ids, int n_ids, float* logp, float* ent, hipStream_t st) {
+  if (rows < 1 || V <= 0 || V % 4 || ldl % 4 || ldl < V || !(temperature >= 0.f) || max_steps < 1 || n_ids < 0 || n_ids > rows) return hipErrorInvalidValue;
+  if (!logits || !tokens || !logp || !step_rows || ((uintptr_t)logits & 15)) return hipErrorInvalidValue;
+  const float inv_temp = temperature == 0.f ? 1.0f : 1.0f / temperature;
+  const TlpRows tr{step_rows, n_ids > 0 ? ids : nullptr};
+  hipLaunchKernelGGL(token_logprob_kernel<TlpRows>, dim3(n_ids > 0 ? n_ids : rows), dim3(TLP_T), 0, st, logits, ldl, V, tokens, inv_temp, pad_id, nullptr,
+                     max_steps, logp, ent, tr);
   return hipGetLastError();
 }
 

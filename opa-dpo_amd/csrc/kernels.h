@@ -236,6 +236,18 @@ hipError_t launch_gather_scores(const float* logits, int ldl, int rows, int V, c
 // per-token log-prob / entropy of the sampled tokens (decode.hip: token_logprob_kernel).  step_ptr (nullable): device step counter, outputs [max_steps, rows]
 hipError_t launch_token_logprobs(const float* logits, int ldl, int rows, int V, const int32_t* tokens, float temperature, int pad_id,
                                  const int32_t* step_ptr, int max_steps, float* logp, float* ent, hipStream_t st);
+// per-row forms of the continuous rollout (decode.hip): a position / step / seed / cap per row, history and log-probs [rows, max_steps]
+hipError_t launch_attn_decode_fused_rows(const bf16_t* qkv, int ld, const float* cosb, const float* sinb, bf16_t* kc, bf16_t* vc, bf16_t* o,
+                                         const uint8_t* key_mask, int B, int nh, int hd, const int32_t* pos_rows, int max_ctx, float scale,
+                                         void* workspace, size_t workspace_bytes, hipStream_t st);
+hipError_t launch_sample_rows(const float* logits, int ldl, int rows, int V, float temperature, int top_k, float top_p, const uint64_t* seed_rows,
+                              int32_t* step_rows, const int32_t* cap_rows, int max_steps, const int32_t* ids, int n_ids, uint8_t* finished, int pad_id,
+                              int eos_id, int32_t* out, int32_t* history, hipStream_t st);
+hipError_t launch_token_logprobs_rows(const float* logits, int ldl, int rows, int V, const int32_t* tokens, float temperature, int pad_id,
+                                      const int32_t* step_rows, int max_steps, const int32_t* ids, int n_ids, float* logp, float* ent, hipStream_t st);
+hipError_t launch_decode_rows_advance(int32_t* pos, const uint8_t* finished, int slots, int max_ctx, hipStream_t st);
+hipError_t launch_decode_rows_admit(const int32_t* slot_ids, const uint64_t* seeds, const int32_t* caps, int n, int Lp, int max_new, int pad_id, int32_t* pos,
+                                    int32_t* step, int32_t* cap, uint64_t* seed, uint8_t* finished, int32_t* history, float* logp, float* ent, hipStream_t st);
 hipError_t launch_attn_decode(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, bf16_t* o, const uint8_t* key_mask,
                               int B, int nh, int hd, int ctx, const int32_t* ctx_ptr, int max_ctx, int ldq, float scale,
                               void* workspace, size_t workspace_bytes, hipStream_t st);

@@ -44,6 +44,9 @@ def rollout_parser() -> argparse.ArgumentParser:
                     help="sampled responses per query off one prefill (1..16, per-device batch x N <= 256; the reference hard-codes 1)")
     ap.add_argument("--output_logprobs", type=_bool, default=False,
                     help="add each response's summed token log-prob, token count and mean token entropy (before the top-k / top-p cuts) to its record")
+    ap.add_argument("--continuous_batching", type=_bool, default=False,
+                    help="run a rollout step's prompts of this rank through one continuous session of rollout_per_device_batch_size decode slots: a "
+                         "finished slot is refilled with the next prompt (not with --num_return_sequences > 1)")
     ap.add_argument("--sample_num", type=int, default=0, help="use only the first N rows (0 = all)")
     ap.add_argument("--max_step", type=int, default=0, help="stop after N rollout steps (0 = whole dataset)")
     ap.add_argument("--image_aspect_ratio", default="pad")
@@ -136,6 +139,10 @@ def run_rollout(args, feedback: Optional[Callable] = None, log=print) -> List[st
     nret = int(getattr(args, "num_return_sequences", 1))
     if not 1 <= nret <= 16 or args.rollout_per_device_batch_size * nret > 256:
         raise SystemExit(f"--num_return_sequences must be in 1..16 with rollout_per_device_batch_size x N <= 256 (got {nret})")
+    cont = bool(getattr(args, "continuous_batching", False))
+    if cont and nret > 1:
+        raise SystemExit(f"--continuous_batching True is not supported with --num_return_sequences > 1 (got {nret}): the n responses of a prompt "
+                         "share one prefill in the static rollout")
     none = args.policy_model_name_or_path in (None, "", "none")
     engine, adapter, tok = _engine(args.base_model_name, args.synthetic, None if none else args.policy_model_name_or_path,
                                    args.lora_rank, args.lora_alpha, args.seed)
@@ -151,6 +158,7 @@ def run_rollout(args, feedback: Optional[Callable] = None, log=print) -> List[st
     gen = Generator(engine, adapter, merge_adapter=True, fuse_swiglu=True)
     sample = generator_sampler(gen, response_len=args.response_len, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                                seed=args.seed + 1000 * rank, num_return_sequences=nret,
+                               **(dict(continuous_slots=args.rollout_per_device_batch_size) if cont else {}),
                                **(dict(output_logprobs=True) if bool(getattr(args, "output_logprobs", False)) else {}))
     mine = list(range(rank, len(ds), world))
     per_step = max(args.rollout_per_device_batch_size, args.rollout_batch_size // world)
@@ -159,8 +167,9 @@ def run_rollout(args, feedback: Optional[Callable] = None, log=print) -> List[st
         if args.max_step and step >= args.max_step:
             break
         idx = mine[s0:s0 + per_step]
-        batches = [collate_query_response([ds[j] for j in idx[b0:b0 + args.rollout_per_device_batch_size]])
-                   for b0 in range(0, len(idx), args.rollout_per_device_batch_size)]
+        # continuous batching: the step's prompts as ONE batch, which the sampler feeds to a session of rollout_per_device_batch_size slots
+        per_batch = len(idx) if cont else args.rollout_per_device_batch_size
+        batches = [collate_query_response([ds[j] for j in idx[b0:b0 + per_batch]]) for b0 in range(0, len(idx), per_batch)]
         files.append(write_rollout_json(args.output_dir, step, rollout_step(batches, tok, sample, feedback, num_return_sequences=nret), rank=rank))
         log(f"step {step}: {len(idx) * nret} rollouts -> {files[-1]}")
     return files

@@ -365,6 +365,99 @@ class CtxEngine(LlavaEngine):
         return out[0] if len(out) == 1 else out
 
     @torch.no_grad()
+    def generate_continuous(self, adapter, queries: torch.Tensor, query_attn_masks: torch.Tensor, image_feats: torch.Tensor, *, slots: int,
+                            max_new_tokens: int, temperature: float, top_k: int, top_p: float, seed: int, eos_token_id: int, pad_token_id: int,
+                            suppress_eos: bool, use_graph: bool, max_new_tokens_per_prompt: Optional[Sequence[int]] = None,
+                            output_logprobs: bool = False, check_every: int = 32, return_schedule: bool = False, num_return_sequences: int = 1,
+                            num_beams: int = 1, logit_bias=None, score_ids=None):
+        """Continuous batching: the N prompts go through ONE session of `slots` decode rows (opadpo_decode_cont_begin); a row whose prompt has
+        finished (EOS, or its cap of max_new_tokens_per_prompt[i] <= max_new_tokens tokens) is refilled with the next waiting prompt at the next
+        check point, every `check_every` steps, instead of decoding pad until the longest row of its batch is done.  Admission goes in ascending
+        slot order, prompts in input order (generate.plan_continuous gives the schedule for known lengths).
+        -> responses [N, max_new_tokens] int64 in prompt order, pad after a prompt finished; with output_logprobs also (logp, ent) fp32 of that
+        shape (-0.0 / 0 where the token is pad); with return_schedule also a list of (slot, steps the session had run at admission) per prompt.
+        Prompt i draws with seed + i under the row id of its slot: its tokens are those of row `slot` of `generate` over a `slots`-row batch that
+        holds prompt i at that row, with seed + i and the same max_new_tokens.  temperature == 0 is greedy as in `generate`.
+        1 <= slots <= 256 (the library refuses others with text)."""
+        if int(num_return_sequences) != 1:
+            raise NotImplementedError("num_return_sequences > 1 is not supported by the continuous rollout: the n responses of a prompt share "
+                                      "one prefill in the static rollout (generate(num_return_sequences=n))")
+        if int(num_beams) != 1:
+            raise NotImplementedError("num_beams > 1 is not supported by the continuous rollout: beam search keeps its own path (generate_beams)")
+        if logit_bias or score_ids is not None:
+            raise NotImplementedError("logit_bias / score_ids are not supported by the continuous rollout: they keep the static rollout (generate)")
+        dev, d = self.dev, self.d
+        N, Q = queries.shape
+        S, T, every = int(slots), int(max_new_tokens), int(check_every)
+        if every < 1:
+            raise ValueError(f"check_every must be >= 1 (got {check_every})")
+        caps = [T] * N if max_new_tokens_per_prompt is None else [int(v) for v in max_new_tokens_per_prompt]
+        if len(caps) != N:
+            raise ValueError(f"max_new_tokens_per_prompt has {len(caps)} entries for {N} prompts")
+        bad = [v for v in caps if not 1 <= v <= T]
+        if bad:
+            raise ValueError(f"max_new_tokens_per_prompt entries must be in 1..max_new_tokens ({T}): got {bad}")
+        if temperature == 0:
+            temperature, top_k, top_p = 1.0, 1, 1.0
+        self._ensure_rope(Q + d.n_patches - 1 + T)
+        aslot = self.adapter_slot(adapter)
+        ids = queries.to(dev).to(torch.int32).contiguous()
+        tmask = query_attn_masks.to(dev).to(torch.uint8).contiguous()
+        feats = image_feats.contiguous()
+        tokens = torch.full((N, T), int(pad_token_id), dtype=torch.int32, device=dev)
+        lp = ent = lp_s = ent_s = None
+        if output_logprobs:
+            lp = torch.full((N, T), -0.0, dtype=torch.float32, device=dev)
+            ent = torch.zeros(N, T, dtype=torch.float32, device=dev)
+            lp_s = torch.empty(max(S, 1), T, dtype=torch.float32, device=dev)          # the session's own rows, [slots, T]
+            ent_s = torch.empty(max(S, 1), T, dtype=torch.float32, device=dev)
+            self._call("opadpo_ctx_set_output_logprobs", _ptr(lp_s), _ptr(ent_s))
+        st = L.stream()
+        schedule: list = [None] * N
+        self._call("opadpo_decode_cont_begin", aslot, S, Q, T, float(temperature), int(top_k), float(top_p), int(eos_token_id), int(pad_token_id),
+                   int(suppress_eos), st)
+        try:
+            occupant: list = [None] * S
+            nxt, steps = 0, 0
+            fin = (C.c_uint8 * S)()
+
+            def admit():
+                nonlocal nxt
+                free = [s_ for s_ in range(S) if occupant[s_] is None][:N - nxt]
+                k = len(free)
+                if not k:
+                    return
+                i0 = nxt
+                self._call("opadpo_decode_cont_admit", k, (C.c_int32 * k)(*free), _ptr(ids[i0:i0 + k]), _ptr(tmask[i0:i0 + k]), _ptr(feats[i0:i0 + k]),
+                           (C.c_uint64 * k)(*[(int(seed) + i) & 0xFFFFFFFFFFFFFFFF for i in range(i0, i0 + k)]), (C.c_int32 * k)(*caps[i0:i0 + k]), st)
+                for j, s_ in enumerate(free):
+                    occupant[s_] = i0 + j
+                    schedule[i0 + j] = (s_, steps)
+                nxt += k
+
+            admit()
+            while any(o is not None for o in occupant):
+                self._call("opadpo_decode_run", every, int(use_graph), st)
+                steps += every
+                self._call("opadpo_decode_cont_poll", fin, st)
+                for s_ in range(S):
+                    i = occupant[s_]
+                    if i is not None and fin[s_]:
+                        self._call("opadpo_decode_cont_retire", s_, _ptr(tokens[i]), _ptr(lp[i]) if output_logprobs else None,
+                                   _ptr(ent[i]) if output_logprobs else None, st)
+                        occupant[s_] = None
+                admit()
+            torch.cuda.current_stream().synchronize()
+        finally:
+            self._call("opadpo_decode_end")
+        out = (tokens.to(torch.int64),)
+        if output_logprobs:
+            out += (lp, ent)
+        if return_schedule:
+            out += (schedule,)
+        return out[0] if len(out) == 1 else out
+
+    @torch.no_grad()
     def generate_beams(self, adapter, queries: torch.Tensor, query_attn_masks: torch.Tensor, image_feats: torch.Tensor, *, num_beams: int,
                        max_new_tokens: int, eos_token_id: int, pad_token_id: int, use_graph: bool, logit_bias=None, score_ids=None):
         """Beam search (HF generate(num_beams=k, do_sample=False, length_penalty=1.0, early_stopping=False)) -> (tokens [B, max_new_tokens]

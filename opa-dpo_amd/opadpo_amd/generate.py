@@ -8,6 +8,9 @@ no collective (the reference's synced_gpus flag is only needed for ZeRO-3; SURVE
 
 Queries are left-padded (utils/data_utils_online_gpt4v.py:100-107) so every row of a batch has the same length and
 the new token of every row sits at the same position: one RoPE position and one cache slot per step.
+
+`Generator.generate_continuous` (continuous batching) gives that up on purpose: its rows are decode slots with a position and a step of
+their own, refilled with the next prompt as they finish; `plan_continuous` is its schedule as host arithmetic.
 """
 from __future__ import annotations
 
@@ -34,6 +37,38 @@ def truncate_after_eos_with_padding(completions: torch.Tensor, eos_token_id: int
         if end is not None:
             rows[r] = row[: end + 1] + [pad_token_id] * (len(row) - end - 1)
     return torch.tensor(rows, dtype=torch.long, device=completions.device)
+
+
+def plan_continuous(lengths: Sequence[int], slots: int, check_every: int = 32):
+    """The schedule of a continuous rollout session (CtxEngine.generate_continuous) for KNOWN response lengths; pure host arithmetic, no GPU.
+    lengths[i] = tokens prompt i generates before it finishes (its EOS included, or its cap).  The session admits prompts in input order
+    into free slots in ascending slot order, first at step 0 and then at every check point, i.e. after every `check_every` decode steps; a prompt
+    admitted when the session had run `a` steps holds token 0 at once and one more per step, so it is finished after a + length - 1 steps and
+    leaves at the first check point at or after that.  -> ([(slot, steps run at admission) per prompt], total decode steps of the session).
+    A static batch costs max(length) - 1 steps per batch of `slots` prompts; the total here is what the same prompts cost refilled."""
+    lengths = [int(v) for v in lengths]
+    slots, check_every = int(slots), int(check_every)
+    if slots < 1 or check_every < 1:
+        raise ValueError(f"slots and check_every must be >= 1 (got {slots}, {check_every})")
+    if any(v < 1 for v in lengths):
+        raise ValueError("every length must be >= 1: a prompt generates at least token 0")
+    n = len(lengths)
+    schedule: list = [None] * n
+    occupant: list = [None] * slots
+    nxt, steps = 0, 0
+    while True:
+        for s in range(slots):                      # admission: free slots in ascending order, prompts in input order
+            if occupant[s] is None and nxt < n:
+                occupant[s] = nxt
+                schedule[nxt] = (s, steps)
+                nxt += 1
+        if all(o is None for o in occupant):
+            return schedule, steps
+        steps += check_every
+        for s in range(slots):                      # the check point: finished prompts leave
+            i = occupant[s]
+            if i is not None and schedule[i][1] + lengths[i] - 1 <= steps:
+                occupant[s] = None
 
 
 class _WeightsOnlyAdapter:
@@ -245,14 +280,54 @@ class Generator:
                     break
         return history.t().contiguous().to(torch.int64)
 
+    @torch.no_grad()
+    def generate_continuous(self, queries: torch.Tensor, query_attn_masks: torch.Tensor, images: Optional[torch.Tensor] = None, *,
+                            image_feats: Optional[torch.Tensor] = None, slots: int, max_new_tokens: int, temperature: float = 1.0, top_k: int = 0,
+                            top_p: float = 1.0, seed: int = 0, eos_token_id: int = EOS_ID, pad_token_id: int = PAD_ID, suppress_eos: bool = False,
+                            max_new_tokens_per_prompt: Optional[Sequence[int]] = None, output_logprobs: bool = False, check_every: int = 32,
+                            return_schedule: bool = False, num_return_sequences: int = 1, num_beams: int = 1,
+                            logit_bias: Optional[Dict[int, float]] = None, score_ids: Optional[Sequence[int]] = None):
+        """Continuous batching (context engine only; ctx.CtxEngine.generate_continuous documents it): the N prompts go through one session of
+        `slots` decode rows, and a row whose prompt finished is refilled with the next prompt.  -> responses [N, max_new_tokens] int64 in prompt
+        order (then logp, ent with output_logprobs, then the per-prompt (slot, admission step) list with return_schedule).
+        num_return_sequences / num_beams above 1 and logit_bias / score_ids keep their static paths: NotImplementedError."""
+        eng = self.engine
+        if not hasattr(eng, "ctx"):
+            raise NotImplementedError("continuous batching runs on the context engine (CtxEngine) only: the op-level LlavaEngine loop is a "
+                                      "cross-check of the static sampling rollout")
+        if int(num_return_sequences) != 1:
+            raise NotImplementedError("num_return_sequences > 1 is not supported by the continuous rollout: the n responses of a prompt share "
+                                      "one prefill in the static rollout (generate(num_return_sequences=n))")
+        if int(num_beams) != 1:
+            raise NotImplementedError("num_beams > 1 is not supported by the continuous rollout: beam search keeps its own path (generate(num_beams=k))")
+        if logit_bias or score_ids is not None:
+            raise NotImplementedError("logit_bias / score_ids are not supported by the continuous rollout: they keep the static rollout (generate)")
+        if image_feats is None:
+            image_feats = eng.encode_images(images)
+        return eng.generate_continuous(self.adapter, queries, query_attn_masks, image_feats, slots=slots, max_new_tokens=max_new_tokens,
+                                       temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, eos_token_id=eos_token_id,
+                                       pad_token_id=pad_token_id, suppress_eos=suppress_eos, use_graph=self.use_graph,
+                                       max_new_tokens_per_prompt=max_new_tokens_per_prompt, output_logprobs=output_logprobs, check_every=check_every,
+                                       return_schedule=return_schedule)
+
     def rollout(self, queries, query_attn_masks, images, *, response_len: int, temperature: float = 1.0, top_k: int = 30,
                 top_p: float = 0.95, seed: int = 0, additional_stop_ids: Sequence[int] = (1577, 29973), num_return_sequences: int = 1,
-                output_logprobs: bool = False):
+                output_logprobs: bool = False, continuous_slots: int = 0):
         """Online_Generator.rollout's tensor part (online_generator.py:292-323): sample, then cut at EOS / '?'.  num_return_sequences = n > 1:
         [B * n, response_len], row i * n + j = sample j of query i.
         output_logprobs: -> (responses, logp, ent), the per-token log-probs / entropies of `generate` with every position whose token is pad AFTER
-        the cut set to -0.0 / 0 (the values of the tokens the cut removed do not belong to the response)."""
+        the cut set to -0.0 / 0 (the values of the tokens the cut removed do not belong to the response).
+        continuous_slots = S > 0: the queries (any number of them) go through one continuous session of S decode slots (generate_continuous)
+        instead of one static batch; query i is then drawn with seed + i.  The cut is the same."""
         extra = {} if num_return_sequences == 1 else dict(num_return_sequences=int(num_return_sequences))
+        if continuous_slots:
+            got = self.generate_continuous(queries, query_attn_masks, images, slots=int(continuous_slots), max_new_tokens=response_len,
+                                           temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, output_logprobs=output_logprobs, **extra)
+            resp = truncate_after_eos_with_padding(got[0] if output_logprobs else got, EOS_ID, PAD_ID, list(additional_stop_ids))
+            if not output_logprobs:
+                return resp
+            pad = resp == PAD_ID
+            return resp, got[1].masked_fill(pad, -0.0), got[2].masked_fill(pad, 0.0)
         if not output_logprobs:
             resp = self.generate(queries, query_attn_masks, images, max_new_tokens=response_len, temperature=temperature,
                                  top_k=top_k, top_p=top_p, seed=seed, **extra)

@@ -69,6 +69,8 @@ SIGNATURES = {
     "opadpo_attn_decode": [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _f, _p, _sz, _p],
     "opadpo_rope_kv_append": [_p, _i, _p, _p, _p, _p, _i, _i, _i, _p, _i, _p],
     "opadpo_attn_decode_fused": [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _f, _p, _sz, _p],
+    "opadpo_attn_decode_fused_rows": [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _f, _p, _sz, _p],
+    "opadpo_sample_rows": [_p, _i, _i, _i, _f, _i, _f, _p, _p, _p, _i, _p, _i, _i, _p, _p, _p],
     "opadpo_sample": [_p, _i, _i, _i, _f, _i, _f, _u64, _u64, _p, _p, _i, _i, _p, _p, _p],
     "opadpo_logit_bias_add": [_p, _i, _i, _i, _p, _p, _p, _i, _p],
     "opadpo_gather_scores": [_p, _i, _i, _i, _p, _p, _i, _f, _i, _f, _p, _p],
@@ -101,6 +103,10 @@ SIGNATURES.update({
     "opadpo_ctx_set_output_logprobs": [_p, _p, _p],
     "opadpo_decode_begin": [_p, _i, _p, _p, _p, _i, _i, _i, _f, _i, _f, _u64, _i, _i, _i, _p, _p],
     "opadpo_decode_begin_n": [_p, _i, _p, _p, _p, _i, _i, _i, _i, _f, _i, _f, _u64, _i, _i, _i, _p, _p],
+    "opadpo_decode_cont_begin": [_p, _i, _i, _i, _i, _f, _i, _f, _i, _i, _i, _p],
+    "opadpo_decode_cont_admit": [_p, _i, _p, _p, _p, _p, _p, _p, _p],
+    "opadpo_decode_cont_poll": [_p, _p, _p],
+    "opadpo_decode_cont_retire": [_p, _i, _p, _p, _p, _p],
     "opadpo_decode_step": [_p, _p],
     "opadpo_decode_run": [_p, _i, _i, _p],
     "opadpo_decode_all_finished": [_p, _p, _p],

@@ -100,13 +100,17 @@ def rollout_step(batches: Iterable[Dict], tokenizer, sample: Callable[[torch.Ten
 
 
 def generator_sampler(generator, *, response_len: int, temperature: float = 1.0, top_k: int = 30, top_p: float = 0.95,
-                      seed: int = 0, num_return_sequences: int = 1, output_logprobs: bool = False) -> Callable:
+                      seed: int = 0, num_return_sequences: int = 1, output_logprobs: bool = False, continuous_slots: int = 0) -> Callable:
     """Sampler over the HIP decode path (`generate.Generator.rollout`); a new seed per batch.  Build the generator with
     `merge_adapter=True` (frozen rollout adapter) or `fuse_swiglu=True` (adapter-free rollout) for the fastest decode step.
     num_return_sequences = N > 1: N responses per query off one prefill, [B * N, response_len] item-major (pass the same N to `rollout_step`).
     output_logprobs: the sampler returns (responses, logp, ent) - `Generator.rollout(..., output_logprobs=True)` - and `rollout_step` adds
-    the per-response log-prob / token count / mean entropy columns."""
+    the per-response log-prob / token count / mean entropy columns.
+    continuous_slots = S > 0: every call runs its queries - hand it a rollout step's whole batch - through one continuous session of S decode
+    slots (`Generator.rollout(..., continuous_slots=S)`); not with num_return_sequences > 1."""
     extra = {} if num_return_sequences == 1 else dict(num_return_sequences=int(num_return_sequences))
+    if continuous_slots:
+        extra["continuous_slots"] = int(continuous_slots)
     if output_logprobs:
         extra["output_logprobs"] = True
     state = {"n": 0}

@@ -11,6 +11,8 @@ POLICY_LORA_DIR=${POLICY_LORA_DIR:-none}
 OUTPUT_DIR=${OUTPUT_DIR:-./output/llava7b_online_generation_subset1}
 NUM_RETURN_SEQUENCES=${NUM_RETURN_SEQUENCES:-1}      # sampled responses per query off one prefill (the reference hard-codes 1)
 OUTPUT_LOGPROBS=${OUTPUT_LOGPROBS:-0}                # 1: per-response summed token log-prob, token count and mean token entropy in every record
+CONTINUOUS_BATCHING=${CONTINUOUS_BATCHING:-0}        # 1: a rank's prompts of a rollout step share one session of rollout_per_device_batch_size decode slots,
+                                                     #    a finished slot is refilled with the next prompt (not with NUM_RETURN_SEQUENCES > 1)
 python opa-dpo_amd/build.py
 torchrun --standalone --nnodes=1 --nproc-per-node=$GPUS_PER_NODE --local-addr 127.0.0.1 \
     opadpo/online_generation_custom.py \
@@ -20,4 +22,5 @@ torchrun --standalone --nnodes=1 --nproc-per-node=$GPUS_PER_NODE --local-addr 12
     --rollout_batch_size 32 --step_batch_size 32 --rollout_per_device_batch_size 4 --reward_model_per_device_batch_size 4 \
     --step_per_device_batch_size 4 --total_epochs 1 --model_max_length 2048 --query_len 128 --response_len 896 --noptepochs 1 \
     --mm_vision_select_layer -2 --ddp_backend nccl --top_k 30 --top_p 0.95 --temperature 1.0 --phase 0 --sample_num 2500 \
-    --num_return_sequences $NUM_RETURN_SEQUENCES --output_logprobs $OUTPUT_LOGPROBS "$@"
+    --num_return_sequences $NUM_RETURN_SEQUENCES --output_logprobs $OUTPUT_LOGPROBS \
+    --continuous_batching $CONTINUOUS_BATCHING "$@"
